@@ -23,9 +23,17 @@ N>1 (torch.distributed.run, one rank per GPU, torch.distributed over RCCL):
   scaling: the total work is fixed); `--weak` instead has every rank bring
   100k queries (global batch N x 100k, labelled weak).
 
-The line names the step's dominant kernel (largest per-step time, HIP events
-on the launch stream) and prices it against its roofline; every kernel stage
-above 10 % of the step is listed with its own time and fraction.
+A plain run sets up, warms up, times `--steps` steps and prints the line
+(value, ms_per_step); `--dump-outputs DIR` also writes the last timed step's
+distances and labels to DIR/D.npy and DIR/I.npy (the inputs are seeded, so two
+builds compare output for output).
+
+With `--full` the same timed steps are followed by the other figures: the line
+also names the step's dominant kernel (largest per-step time, HIP events on
+the launch stream) and prices it against its roofline; every kernel stage
+above 10 % of the step is listed with its own time and fraction; and it
+carries recall@10, the host-buffer rate (`pcie_inclusive`), the CPU baseline
+and, at N > 1, `rccl_shards`.
 """
 from __future__ import annotations
 
@@ -142,8 +150,13 @@ def cpu_baseline(args, cfg, amd, index, xq, I_gpu, k, nprobe):
     ef = cfg.get("efSearch")
     ref = None
     try:
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        import reflib  # noqa: E402  (test infrastructure: the CPU baseline leg)
+        # loaded by file name: oracle/ on sys.path would make oracle/oracle.py
+        # the top-level module `oracle` and break load_oracle() below
+        import importlib.util
+        spec = importlib.util.spec_from_file_location(
+            "reflib", os.path.join(ROOT, "oracle", "reflib.py"))
+        reflib = importlib.util.module_from_spec(spec)  # (test infrastructure: the CPU baseline leg)
+        spec.loader.exec_module(reflib)
         if reflib.available():
             import tempfile
             fn = os.path.join(tempfile.gettempdir(), f"bench_ref_{os.getpid()}.faiss")
@@ -279,12 +292,38 @@ def kernel_roofline(name, ms, work, config):
     return r
 
 
-def main():
+def dump_outputs(dirname, rank, D_t, I_t):
+    """What the timed path left in its caller's buffers after the last timed
+    step, as <dirname>/D.npy (float32 distances) and <dirname>/I.npy (the
+    int64 labels as float64, exact below 2^53); rank r > 0 of a multi-GPU run
+    writes D.rank<r>.npy / I.rank<r>.npy.  A seeded sample of rows when the
+    two would pass 64 MB (none of the configs do)."""
+    D = D_t.cpu().numpy().astype(np.float32, copy=False)
+    I = I_t.cpu().numpy().astype(np.float64)
+    max_rows = (64 << 20) // (12 * D.shape[1])
+    if D.shape[0] > max_rows:
+        rows = np.sort(np.random.default_rng(2024).choice(D.shape[0], max_rows, replace=False))
+        D, I = D[rows], I[rows]
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f".rank{rank}" if rank else ""
+    np.save(os.path.join(dirname, f"D{sfx}.npy"), D)
+    np.save(os.path.join(dirname, f"I{sfx}.npy"), I)
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: the per-kernel breakdown and rooflines, "
+                         "recall@10, the host-buffer (pcie_inclusive) rate, the CPU baseline "
+                         "and, at N > 1, the rccl_shards figure.  Without it the run sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the distances and labels of the last "
+                         "timed step to DIR/D.npy (float32) and DIR/I.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--recall-queries", type=int, default=1000)
@@ -302,7 +341,15 @@ def main():
                     help="override the config's quantizer efSearch (HNSW configs)")
     ap.add_argument("--weak", action="store_true",
                     help="c5: every rank brings nq queries (global batch N x nq)")
+    return ap
+
+
+def main():
+    ap = build_parser()
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    full = args.full
     cfg = CONFIGS[args.config]
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -347,7 +394,7 @@ def main():
         nq_glob = nq * world
     # recall queries: the first of rank 0's (every rank of a sharded run
     # computes its shard's exact top-k for them; rank 0 merges)
-    nr = min(args.recall_queries, nq_loc)
+    nr = min(args.recall_queries, nq_loc) if full else 0
     # (float_rand's blocks depend on n: rank 0's rows are re-derived from its
     # whole set, not from a shorter call)
     xr = None
@@ -443,7 +490,10 @@ def main():
         timed: the per-step breakdown), then exactly `steps` steps between a
         barrier + synchronize on both sides, with only the dominant stage
         timed.  Returns (max elapsed over ranks, breakdown, dominant stage,
-        its ms per step in the timed region)."""
+        its ms per step in the timed region).  (The same with and without
+        --full: `value` is measured on one path.  A/B on one MI355X, c2, 3000
+        steps, alternating: 0.2689 ms per step so, 0.2731 ms with the stage
+        timers off.)"""
         step_fn()
         torch.cuda.synchronize()
         nb_steps = max(1, warmup - 1)
@@ -482,6 +532,37 @@ def main():
     elapsed, brk, dom, dom_ms = run_timed(step, index, args.steps, args.warmup)
     ms_per_step = elapsed / args.steps * 1e3
     qps = nq_glob * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, D_t, I_t)
+
+    par = (f"replicas{world}" if replicas else
+           f"shards{world}" if world > 1 else "single")
+    out = {
+        "metric": "queries/sec @ recall@10, IVF4096 d=128 nq=10k nprobe=32; 1/2/4/8 GPUs"
+        if args.config == "c2" else f"queries/sec, {cfg['workload']}",
+        "value": qps, "unit": "queries/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        # "weak": every GPU brings its own nq queries (replicas / --shard /
+        # c5 --weak); "strong": c5's 100M set and 100k-query batch split
+        # over the GPUs
+        "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic", "full": full,
+        "config": {"workload": cfg["workload"], "d": d, "nb": nb,
+                   "vectors_per_gpu": len(ids), "nq_per_gpu": nq_loc,
+                   "nprobe": nprobe, "k": k, "global_batch": nq_glob,
+                   "parallelism": par,
+                   "efSearch": cfg.get("efSearch"),
+                   "grid_point": bool(args.nprobe or args.efsearch)},
+    }
+    if not full:
+        # the plain run ends here: recall, the kernel breakdown and rooflines,
+        # the host-buffer rate, the CPU baseline and the rccl_shards figure
+        # are --full's
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- the step's algorithmic work (this rank), for the roofline models
     cd_h = torch.empty((nq_loc, nprobe), dtype=torch.float32, device=dev)
@@ -622,31 +703,11 @@ def main():
         cpu = cpu_baseline(args, cfg, amd, index, xq, I_t.cpu().numpy(), k, nprobe)
 
     if rank == 0:
-        par = (f"replicas{world}" if replicas else
-               f"shards{world}" if world > 1 else "single")
-        out = {
-            "metric": "queries/sec @ recall@10, IVF4096 d=128 nq=10k nprobe=32; 1/2/4/8 GPUs"
-            if args.config == "c2" else f"queries/sec, {cfg['workload']}",
-            "value": qps, "unit": "queries/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-            # "weak": every GPU brings its own nq queries (replicas / --shard /
-            # c5 --weak); "strong": c5's 100M set and 100k-query batch split
-            # over the GPUs
-            "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": cfg["workload"], "d": d, "nb": nb,
-                       "vectors_per_gpu": len(ids), "nq_per_gpu": nq_loc,
-                       "nprobe": nprobe, "k": k, "global_batch": nq_glob,
-                       "parallelism": par, "recall_at_10": recall,
-                       "recall_ground_truth": gt_note if nr else None,
-                       "candidates_per_query": cand_per_q,
-                       "efSearch": cfg.get("efSearch"),
-                       "grid_point": bool(args.nprobe or args.efsearch)},
-            "roofline": roofline,
-            "kernels": kernels,
-            "cpu_baseline": cpu,
-            "pcie_inclusive": pcie,
-        }
+        out["config"].update({"recall_at_10": recall,
+                              "recall_ground_truth": gt_note if nr else None,
+                              "candidates_per_query": cand_per_q})
+        out.update({"roofline": roofline, "kernels": kernels, "cpu_baseline": cpu,
+                    "pcie_inclusive": pcie})
         if shard_fig is not None:
             out["rccl_shards"] = shard_fig
         print(json.dumps(out), flush=True)

@@ -7,8 +7,8 @@ G=hnsw-ivf_amd/lib/ab/libfaiss_amd_gate.so
 FAISS_AMD_LIB=$G timeout -k 10 600 python -u -m pytest tests/test_gpu_golden.py tests/test_gpu_ref_fixtures.py tests/test_gpu_wide_nprobe.py tests/test_gpu_idselector.py -x -q -m gpu --timeout 300 --timeout-method thread > gpurun_out/gate_suite.log 2>&1
 rc=$?; tail -2 gpurun_out/gate_suite.log; [ $rc -eq 0 ] || exit $rc
 for c in ${CFGS:-c2 c3 c5}; do
-  extra=""; st="--steps 200 --warmup 5"
-  [ "$c" = c5 ] && { extra="--shard-of 8"; st="--steps 20 --warmup 2"; }
+  extra=""; st="--full --steps 200 --warmup 5"
+  [ "$c" = c5 ] && { extra="--shard-of 8"; st="--full --steps 20 --warmup 2"; }
   for v in default gate; do
     L=""; [ $v = gate ] && L=$G
     FAISS_AMD_LIB=$L timeout -k 10 400 python -u bench.py --config $c $extra $st --no-cpu-baseline --recall-queries 0 > gpurun_out/gate_${c}_$v.json 2> gpurun_out/gate_${c}_$v.err

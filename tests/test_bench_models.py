@@ -33,6 +33,27 @@ def test_pmc_traffic_takes_the_last_launched_grid(tmp_path, monkeypatch):
     assert bench.pmc_traffic("c4", "ivf_flat_scan") == (None, None)
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    ap = bench.build_parser()
+    a = ap.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = ap.parse_args(["--full", "--dump-outputs", "somewhere"])
+    assert a.full and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    import numpy as np
+    import torch
+    D = torch.arange(12, dtype=torch.float32).reshape(4, 3) / 7
+    I = torch.tensor([[3, 1, -1], [2 ** 40, 0, 5], [7, 8, 9], [1, 2, 3]], dtype=torch.int64)
+    bench.dump_outputs(str(tmp_path / "o"), 0, D, I)
+    bench.dump_outputs(str(tmp_path / "o"), 2, D, I)
+    Dn, In = np.load(tmp_path / "o" / "D.npy"), np.load(tmp_path / "o" / "I.npy")
+    assert Dn.dtype == np.float32 and np.array_equal(Dn, D.numpy())
+    assert In.dtype == np.float64 and np.array_equal(In.astype(np.int64), I.numpy())
+    assert sorted(os.listdir(tmp_path / "o")) == ["D.npy", "D.rank2.npy", "I.npy", "I.rank2.npy"]
+
+
 def test_hnsw_roofline_prices_rows_read():
     work = {"hnsw_ndis": 1000.0, "hnsw_fp32_rows": 150.0, "hnsw_q8_rows": 900.0,
             "hnsw_nhops": 40.0, "d": 128}
