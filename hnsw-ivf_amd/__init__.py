@@ -197,6 +197,10 @@ def _declare(L):
         "faiss_amd_IndexIVFPQ_new_with": (C.c_int, [C.POINTER(_P), _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]),
         "faiss_amd_IndexIVFPQ_pq_centroids": (None, [_P, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t)]),
         "faiss_amd_IndexIVFPQ_info": (C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "faiss_IndexIVFScalarQuantizer_new_with_metric": (C.c_int, [C.POINTER(_P), _P, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int]),
+        "faiss_IndexIVFScalarQuantizer_add_core": (C.c_int, [_P, _I64, _P, _P, _P]),
+        "faiss_amd_IndexIVFScalarQuantizer_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "faiss_amd_IndexIVFScalarQuantizer_trained": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t)]),
         "faiss_amd_IndexHNSWFlat_new_with": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int]),
         "faiss_amd_IndexHNSW_efSearch": (C.c_int, [_P]),
         "faiss_amd_IndexHNSW_set_efSearch": (None, [_P, C.c_int]),
@@ -681,6 +685,56 @@ class IndexIVFPQ(IndexIVF):
             info["M"], 1 << info["nbits"], dsub).copy()
 
 
+# faiss/impl/ScalarQuantizer.h:27-38 (the two served qtypes)
+QT_8bit = 0
+QT_fp16 = 4
+
+
+class IndexIVFScalarQuantizer(IndexIVF):
+    """faiss/IndexScalarQuantizer.h:65-125: QT_8bit / QT_fp16, d % 8 == 0."""
+
+    def __init__(self, quantizer=None, d=None, nlist=None, qtype=QT_8bit, metric=METRIC_L2,
+                 by_residual=True, handle=None, owner=None):
+        if handle is None:
+            p = C.c_void_p()
+            _check(lib().faiss_IndexIVFScalarQuantizer_new_with_metric(
+                C.byref(p), quantizer.h, d, nlist, int(qtype), metric, int(bool(by_residual))))
+            handle = p
+            self._q = quantizer
+        super().__init__(handle, owner)
+
+    def _info(self):
+        qt, br = C.c_int(), C.c_int()
+        _check(lib().faiss_amd_IndexIVFScalarQuantizer_info(self.h, C.byref(qt), C.byref(br)))
+        return qt.value, bool(br.value)
+
+    @property
+    def qtype(self):
+        return self._info()[0]
+
+    @property
+    def by_residual(self):
+        return self._info()[1]
+
+    def sq_trained(self):
+        """ScalarQuantizer::trained as float32 (QT_8bit: vmin [d] then vdiff [d];
+        QT_fp16: empty)."""
+        p = C.POINTER(C.c_float)()
+        n = C.c_size_t(0)
+        _check(lib().faiss_amd_IndexIVFScalarQuantizer_trained(self.h, C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=np.float32)
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy()
+
+    def add_core(self, x, ids, precomputed_idx):
+        """IndexIVFScalarQuantizer::add_core: add x to the lists precomputed_idx names."""
+        x = _f32(x)
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64)
+        pre = np.ascontiguousarray(precomputed_idx, dtype=np.int64)
+        _check(lib().faiss_IndexIVFScalarQuantizer_add_core(
+            self.h, x.shape[0], _ptr(x), _ptr(ids) if ids is not None else None, _ptr(pre)))
+
+
 class IndexShardsIVF(IndexIVF):
     """faiss/IndexShardsIVF.h: shards sharing one coarse quantizer; shards on
     other devices than the quantizer are searched over RCCL (shards.cpp)."""
@@ -841,6 +895,7 @@ def _wrap(h, owner=None):
     if t == "IndexShardsIVF":
         return IndexShardsIVF.__new__(IndexShardsIVF)._init_from(h, owner)
     cls = {"IndexIVFPQ": IndexIVFPQ, "IndexIVFFlat": IndexIVFFlat,
+           "IndexIVFScalarQuantizer": IndexIVFScalarQuantizer,
            "IndexHNSWFlat": IndexHNSWFlat, "IndexFlat": IndexFlat}.get(t)
     if cls is None:
         return Index(h, owner)

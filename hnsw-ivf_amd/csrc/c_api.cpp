@@ -304,6 +304,7 @@ const char* faiss_amd_Index_type(const FaissIndex* i) {
     const Index* x = IX(i);
     if (dynamic_cast<const IndexShardsIVF*>(x)) return "IndexShardsIVF";
     if (dynamic_cast<const IndexIVFPQ*>(x)) return "IndexIVFPQ";
+    if (dynamic_cast<const IndexIVFScalarQuantizer*>(x)) return "IndexIVFScalarQuantizer";
     if (dynamic_cast<const IndexIVFFlat*>(x)) return "IndexIVFFlat";
     if (dynamic_cast<const IndexHNSW*>(x)) return "IndexHNSWFlat";
     if (dynamic_cast<const IndexFlat*>(x)) return "IndexFlat";
@@ -493,6 +494,80 @@ int faiss_amd_IndexIVFPQ_set_use_precomputed_table(FaissIndexIVFPQ* index, int v
     FAISS_THROW_IF_NOT_MSG(v == 0 || (v == 1 && pq->by_residual && pq->metric_type == faiss_amd::METRIC_L2),
                            "use_precomputed_table: 0, or 1 for by-residual L2");
     pq->use_precomputed_table = v;
+    C_CATCH
+}
+
+// ---------------- IndexIVFScalarQuantizer (c_api/IndexScalarQuantizer_c.h:51-91)
+static IndexIVFScalarQuantizer* SQm(FaissIndexIVFScalarQuantizer* i) {
+    auto r = dynamic_cast<IndexIVFScalarQuantizer*>(IX(i));
+    FAISS_THROW_IF_NOT_MSG(r, "not an IndexIVFScalarQuantizer");
+    return r;
+}
+FaissIndexIVFScalarQuantizer* faiss_IndexIVFScalarQuantizer_cast(FaissIndex* index) {
+    return dynamic_cast<IndexIVFScalarQuantizer*>(IX(index)) ? index : nullptr;
+}
+void faiss_IndexIVFScalarQuantizer_free(FaissIndexIVFScalarQuantizer* obj) { delete IX(obj); }
+int faiss_IndexIVFScalarQuantizer_new(FaissIndexIVFScalarQuantizer** p_index) {
+    C_TRY std::unique_ptr<Index> q(new IndexFlatL2(0));
+    auto ix = new IndexIVFScalarQuantizer(q.get(), 0, 0, ScalarQuantizer::QT_8bit);
+    q.release();
+    ix->own_fields = true;
+    *p_index = FX(ix);
+    C_CATCH
+}
+int faiss_IndexIVFScalarQuantizer_new_with(FaissIndexIVFScalarQuantizer** p_index,
+                                           FaissIndex* quantizer, idx_t d, size_t nlist,
+                                           FaissQuantizerType qt) {
+    C_TRY FAISS_THROW_IF_NOT(d >= 0);
+    *p_index = FX(new IndexIVFScalarQuantizer(IX(quantizer), (size_t)d, nlist,
+                                              (ScalarQuantizer::QuantizerType)qt));
+    C_CATCH
+}
+int faiss_IndexIVFScalarQuantizer_new_with_metric(FaissIndexIVFScalarQuantizer** p_index,
+                                                  FaissIndex* quantizer, size_t d, size_t nlist,
+                                                  FaissQuantizerType qt, FaissMetricType metric,
+                                                  int encode_residual) {
+    C_TRY* p_index = FX(new IndexIVFScalarQuantizer(IX(quantizer), d, nlist,
+                                                    (ScalarQuantizer::QuantizerType)qt,
+                                                    (MetricType)metric, encode_residual != 0));
+    C_CATCH
+}
+size_t faiss_IndexIVFScalarQuantizer_nlist(const FaissIndexIVFScalarQuantizer* i) {
+    return faiss_IndexIVF_nlist(i);
+}
+size_t faiss_IndexIVFScalarQuantizer_nprobe(const FaissIndexIVFScalarQuantizer* i) {
+    return faiss_IndexIVF_nprobe(i);
+}
+void faiss_IndexIVFScalarQuantizer_set_nprobe(FaissIndexIVFScalarQuantizer* i, size_t v) {
+    faiss_IndexIVF_set_nprobe(i, v);
+}
+FaissIndex* faiss_IndexIVFScalarQuantizer_quantizer(const FaissIndexIVFScalarQuantizer* i) {
+    return faiss_IndexIVF_quantizer(i);
+}
+int faiss_IndexIVFScalarQuantizer_own_fields(const FaissIndexIVFScalarQuantizer* i) {
+    return faiss_IndexIVF_own_fields(i);
+}
+void faiss_IndexIVFScalarQuantizer_set_own_fields(FaissIndexIVFScalarQuantizer* i, int v) {
+    faiss_IndexIVF_set_own_fields(i, v);
+}
+int faiss_IndexIVFScalarQuantizer_add_core(FaissIndexIVFScalarQuantizer* index, idx_t n,
+                                           const float* x, const idx_t* xids,
+                                           const idx_t* precomputed_idx) {
+    C_TRY SQm(index)->add_core(n, x, xids, precomputed_idx);
+    C_CATCH
+}
+int faiss_amd_IndexIVFScalarQuantizer_info(const FaissIndexIVFScalarQuantizer* index, int* qtype,
+                                           int* by_residual) {
+    C_TRY auto s = SQm(const_cast<FaissIndexIVFScalarQuantizer*>(index));
+    *qtype = (int)s->sq.qtype;
+    *by_residual = s->by_residual ? 1 : 0;
+    C_CATCH
+}
+int faiss_amd_IndexIVFScalarQuantizer_trained(const FaissIndexIVFScalarQuantizer* index,
+                                              const float** p_trained, size_t* p_size) {
+    C_TRY auto s = SQm(const_cast<FaissIndexIVFScalarQuantizer*>(index));
+    *p_trained = s->sq.trained.data();
+    *p_size = s->sq.trained.size();
     C_CATCH
 }
 
@@ -700,7 +775,9 @@ int faiss_read_index_fname(const char* fname, int io_flags, FaissIndex** p_out) 
 // type of this library round-trips its on-disk form byte for byte, so the
 // copy goes through it (an anonymous temporary file)
 int faiss_clone_index(const FaissIndex* idx, FaissIndex** p_out) {
-    C_TRY FILE* f = tmpfile();
+    C_TRY FAISS_THROW_IF_NOT_MSG(!dynamic_cast<const IndexIVFScalarQuantizer*>(IX(idx)),
+                                 "clone_index is not supported on IndexIVFScalarQuantizer");
+    FILE* f = tmpfile();
     FAISS_THROW_IF_NOT_MSG(f, "clone_index: no temporary file");
     std::unique_ptr<FILE, int (*)(FILE*)> guard(f, fclose);
     write_index(IX(idx), f);

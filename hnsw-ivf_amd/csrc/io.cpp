@@ -10,6 +10,9 @@
 //   IwFl    = IVF hdr, invlists                               (:631-638)
 //   IwPQ    = IVF hdr, by_residual:u8, code_size:size_t, PQ (d,M,nbits:size_t,
 //             vector<float> centroids), invlists               (:697-705,155-160)
+//   IwSq    = IVF hdr, ScalarQuantizer (qtype:i32 rangestat:i32 rangestat_arg:f32
+//             d:size_t code_size:size_t vector<float> trained), code_size:size_t,
+//             by_residual:u8, invlists                          (:234-241,640-648)
 //   ilar    = nlist:size_t, code_size:size_t, "full"+vector<size_t> sizes |
 //             "sprs"+vector<size_t>(list,size pairs), then per non-empty list
 //             codes then ids                                  (:243-297)
@@ -481,6 +484,19 @@ void write_index_impl(const Index* idx, Writer& w) {
         w.one<size_t>(pq->pq.nbits);
         w.vec(pq->pq.centroids);
         write_invlists(pq->invlists.get(), w);
+    } else if (auto sq = dynamic_cast<const IndexIVFScalarQuantizer*>(idx)) {
+        // faiss/impl/index_write.cpp:234-241, 640-648
+        w.one(fourcc("IwSq"));
+        write_ivf_header(sq, w);
+        w.one<int32_t>((int32_t)sq->sq.qtype);
+        w.one<int32_t>((int32_t)sq->sq.rangestat);
+        w.one<float>(sq->sq.rangestat_arg);
+        w.one<size_t>(sq->sq.d);
+        w.one<size_t>(sq->sq.code_size);
+        w.vec(sq->sq.trained);
+        w.one<size_t>(sq->code_size);
+        w.one<uint8_t>(sq->by_residual ? 1 : 0);
+        write_invlists(sq->invlists.get(), w);
     } else {
         FAISS_THROW_MSG("don't know how to serialize this type of index");
     }
@@ -524,7 +540,7 @@ Index* read_index_impl(Reader& r, int io_flags) {
         ix->device = stf->device;
         return ix;
     }
-    if (h == fourcc("IwFl") || h == fourcc("IwPQ")) {
+    if (h == fourcc("IwFl") || h == fourcc("IwPQ") || h == fourcc("IwSq")) {
         Header hd = read_header(r);
         size_t nlist = r.one<size_t>();
         size_t nprobe = r.one<size_t>();
@@ -537,6 +553,33 @@ Index* read_index_impl(Reader& r, int io_flags) {
         IndexIVF* ivf;
         if (h == fourcc("IwFl")) {
             ivf = new IndexIVFFlat(q, hd.d, nlist, (MetricType)hd.metric);
+        } else if (h == fourcc("IwSq")) {
+            // faiss/impl/index_read.cpp:353-361, 815-826
+            std::unique_ptr<Index> qguard(q);
+            const int32_t qtype = r.one<int32_t>();
+            const int32_t rangestat = r.one<int32_t>();
+            const float rs_arg = r.one<float>();
+            const size_t sd = r.one<size_t>(), scs = r.one<size_t>();
+            // the constructor throws, naming the qtype / d, unless served
+            ScalarQuantizer::check_supported(qtype, (size_t)hd.d);
+            FAISS_THROW_IF_NOT_FMT(sd == (size_t)hd.d, "IwSq: ScalarQuantizer d = %zu, index d = %d",
+                                   sd, hd.d);
+            auto sqi = std::make_unique<IndexIVFScalarQuantizer>(
+                    q, hd.d, nlist, (ScalarQuantizer::QuantizerType)qtype, (MetricType)hd.metric);
+            sqi->sq.rangestat = (ScalarQuantizer::RangeStat)rangestat;
+            sqi->sq.rangestat_arg = rs_arg;
+            r.vec(sqi->sq.trained);
+            const size_t code_size = r.one<size_t>();
+            sqi->by_residual = r.one<uint8_t>() != 0;
+            FAISS_THROW_IF_NOT_FMT(scs == sqi->sq.code_size && code_size == sqi->code_size,
+                                   "IwSq: code_size %zu / %zu, expected %zu", scs, code_size,
+                                   sqi->sq.code_size);
+            const size_t nt = qtype == ScalarQuantizer::QT_8bit ? 2 * (size_t)hd.d : 0;
+            FAISS_THROW_IF_NOT_FMT(!hd.is_trained || sqi->sq.trained.size() == nt,
+                                   "IwSq: %zu trained values, expected %zu",
+                                   sqi->sq.trained.size(), nt);
+            qguard.release();
+            ivf = sqi.release();
         } else {
             bool by_res = r.one<uint8_t>() != 0;
             size_t code_size = r.one<size_t>();
@@ -662,6 +705,24 @@ Index* index_factory(int d, const char* description, MetricType metric) {
             std::string tail = enc.substr(p2);
             FAISS_THROW_IF_NOT_MSG(tail.empty() || tail == "np", "unsupported PQ spec " + enc);
             ivf = new IndexIVFPQ(q, d, nlist, M, nbits, metric);
+        } else if (enc.rfind("SQ", 0) == 0) {
+            // faiss/index_factory.cpp sq_types; the constructor rejects the
+            // qtypes and dimensions this path does not serve, naming them
+            static const struct {
+                const char* name;
+                ScalarQuantizer::QuantizerType qt;
+            } sq_types[] = {{"SQ8", ScalarQuantizer::QT_8bit},
+                            {"SQ4", ScalarQuantizer::QT_4bit},
+                            {"SQ6", ScalarQuantizer::QT_6bit},
+                            {"SQfp16", ScalarQuantizer::QT_fp16},
+                            {"SQbf16", ScalarQuantizer::QT_bf16},
+                            {"SQ8_direct_signed", ScalarQuantizer::QT_8bit_direct_signed},
+                            {"SQ8_direct", ScalarQuantizer::QT_8bit_direct}};
+            int found = -1;
+            for (int i = 0; i < 7; i++)
+                if (enc == sq_types[i].name) found = i;
+            FAISS_THROW_IF_NOT_MSG(found >= 0, "unsupported IVF encoding " + enc);
+            ivf = new IndexIVFScalarQuantizer(q, d, nlist, sq_types[found].qt, metric);
         } else {
             FAISS_THROW_MSG("unsupported IVF encoding " + enc);
         }

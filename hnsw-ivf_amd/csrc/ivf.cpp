@@ -1,4 +1,5 @@
-// ivf.cpp — IndexIVF / IndexIVFFlat / IndexIVFPQ / IndexShardsIVF host side.
+// ivf.cpp — IndexIVF / IndexIVFFlat / IndexIVFPQ / IndexIVFScalarQuantizer /
+// IndexShardsIVF host side.
 //
 // Reference: faiss/IndexIVF.cpp:303-397 (search), :399-723
 // (search_preassigned), :187-285 (add), faiss/IndexIVFFlat.cpp,
@@ -14,6 +15,7 @@
 
 #include "../../include/faiss_amd.h"
 #include "kernels.h"
+#include "sq_ref.h"
 
 namespace faiss_amd {
 
@@ -94,7 +96,9 @@ IndexIVF::~IndexIVF() {
 }
 
 int IndexIVF::device_code_stride() const {
-    // IVF-Flat keeps 16-B aligned float rows; PQ keeps 4-B aligned code rows
+    // IVF-Flat keeps 16-B aligned float rows; PQ keeps 4-B aligned code rows;
+    // SQ rows are read 16 bytes per load (kernels_sq.hip)
+    if (dynamic_cast<const IndexIVFScalarQuantizer*>(this)) return (int)roundup(code_size, 16);
     return (int)roundup(code_size, 4);
 }
 
@@ -141,7 +145,8 @@ void IndexIVF::train(idx_t n, const float* x) {
     // train the encoder on (a subset of) the assigned training vectors
     std::vector<idx_t> assign(n);
     std::vector<float> dis(n);
-    if (by_residual || dynamic_cast<IndexIVFPQ*>(this)) {
+    if (by_residual || dynamic_cast<IndexIVFPQ*>(this) ||
+        dynamic_cast<IndexIVFScalarQuantizer*>(this)) {
         quantizer->search(n, x, 1, dis.data(), assign.data());
         train_encoder(n, x, assign.data());
     }
@@ -1815,6 +1820,223 @@ void IndexIVFPQ::exact_args(void* p) const {
     a.pq.ldcent = ld();
     a.pq.codes = d_codes_.as<uint8_t>();
     a.pq.cs = device_code_stride();
+}
+
+// ---------------------------------------------------------------- SQ
+// faiss/impl/ScalarQuantizer.cpp, faiss/IndexScalarQuantizer.cpp:119-180; the
+// arithmetic is csrc/sq_ref.h.
+const char* ScalarQuantizer::qtype_name(int qt) {
+    static const char* names[] = {"QT_8bit",        "QT_4bit", "QT_8bit_uniform",
+                                  "QT_4bit_uniform", "QT_fp16", "QT_8bit_direct",
+                                  "QT_6bit",        "QT_bf16", "QT_8bit_direct_signed"};
+    return qt >= 0 && qt < 9 ? names[qt] : "unknown qtype";
+}
+
+void ScalarQuantizer::check_supported(int qt, size_t d) {
+    FAISS_THROW_IF_NOT_FMT(qt == QT_8bit || qt == QT_fp16,
+                           "ScalarQuantizer qtype %s (%d) is not supported on this path "
+                           "(QT_8bit and QT_fp16 are)",
+                           qtype_name(qt), qt);
+    const bool d_ok = (d & 7) == 0;  // (0: the C API's empty index)
+    FAISS_THROW_IF_NOT_FMT(d_ok,
+                           "ScalarQuantizer %s: d = %zu is not supported on this path "
+                           "(d must be a multiple of 8)",
+                           qtype_name(qt), d);
+}
+
+ScalarQuantizer::ScalarQuantizer(size_t d_, QuantizerType qt) : qtype(qt), d(d_) {
+    check_supported((int)qt, d_);
+    set_derived_sizes();
+}
+
+void ScalarQuantizer::set_derived_sizes() {  // ScalarQuantizer.cpp:1150-1180
+    bits = qtype == QT_fp16 ? 16 : 8;
+    code_size = qtype == QT_fp16 ? d * 2 : d;
+}
+
+void ScalarQuantizer::train(size_t n, const float* x) {
+    if (qtype != QT_8bit) return;  // fp16: nothing to train
+    FAISS_THROW_IF_NOT_MSG(rangestat == RS_minmax,
+                           "ScalarQuantizer: only RS_minmax training is supported");
+    FAISS_THROW_IF_NOT(n > 0);
+    trained.resize(2 * d);
+    float* vmin = trained.data();
+    float* vmax = trained.data() + d;
+    memcpy(vmin, x, sizeof(float) * d);
+    memcpy(vmax, x, sizeof(float) * d);
+    for (size_t i = 1; i < n; i++) {
+        const float* xi = x + i * d;
+        for (size_t j = 0; j < d; j++) {
+            if (xi[j] < vmin[j]) vmin[j] = xi[j];
+            if (xi[j] > vmax[j]) vmax[j] = xi[j];
+        }
+    }
+    for (size_t j = 0; j < d; j++) {
+        const float vexp = (vmax[j] - vmin[j]) * rangestat_arg;
+        vmin[j] -= vexp;
+        vmax[j] += vexp;
+        vmax[j] = vmax[j] - vmin[j];  // vdiff
+    }
+}
+
+void ScalarQuantizer::compute_codes(const float* x, uint8_t* codes, size_t n) const {
+    if (qtype == QT_fp16) {
+        for (size_t i = 0; i < n * d; i++) {
+            const uint16_t h = kern::sq_float_to_half(x[i]);
+            memcpy(codes + 2 * i, &h, 2);
+        }
+        return;
+    }
+    FAISS_THROW_IF_NOT_MSG(trained.size() == 2 * d, "ScalarQuantizer is not trained");
+    const float *vmin = trained.data(), *vdiff = trained.data() + d;
+    for (size_t i = 0; i < n; i++)
+        for (size_t j = 0; j < d; j++)
+            codes[i * d + j] = kern::sq_encode8(x[i * d + j], vmin[j], vdiff[j]);
+}
+
+void ScalarQuantizer::decode(const uint8_t* codes, float* x, size_t n) const {
+    if (qtype == QT_fp16) {
+        for (size_t i = 0; i < n * d; i++) {
+            uint16_t h;
+            memcpy(&h, codes + 2 * i, 2);
+            x[i] = kern::sq_half_to_float(h);
+        }
+        return;
+    }
+    FAISS_THROW_IF_NOT_MSG(trained.size() == 2 * d, "ScalarQuantizer is not trained");
+    const float *vmin = trained.data(), *vdiff = trained.data() + d;
+    for (size_t i = 0; i < n; i++)
+        for (size_t j = 0; j < d; j++)
+            x[i * d + j] = kern::sq_recons8(codes[i * d + j], vmin[j], vdiff[j]);
+}
+
+IndexIVFScalarQuantizer::IndexIVFScalarQuantizer(Index* q, size_t d_, size_t nl,
+                                                 ScalarQuantizer::QuantizerType qtype,
+                                                 MetricType metric, bool by_res)
+        : IndexIVF(q, d_, nl, 0, metric), sq(d_, qtype) {
+    code_size = sq.code_size;
+    invlists = std::make_unique<ArrayInvertedLists>(nlist, code_size);
+    by_residual = by_res;
+    is_trained = false;
+}
+
+void IndexIVFScalarQuantizer::train_encoder(idx_t n, const float* x, const idx_t* assign) {
+    // faiss/IndexIVF.cpp train: the encoder sees residuals when by_residual
+    if (by_residual) {
+        std::vector<float> resid((size_t)n * d), c(d);
+        for (idx_t i = 0; i < n; i++) {
+            const float* xi = x + (size_t)i * d;
+            float* ri = resid.data() + (size_t)i * d;
+            FAISS_THROW_IF_NOT_MSG(assign[i] >= 0, "training vector without a list");
+            quantizer->reconstruct(assign[i], c.data());
+            for (int j = 0; j < d; j++) ri[j] = xi[j] - c[j];
+        }
+        sq.train((size_t)n, resid.data());
+    } else {
+        sq.train((size_t)n, x);
+    }
+    std::lock_guard<std::recursive_mutex> g(mu_);
+    dirty_ = true;
+}
+
+void IndexIVFScalarQuantizer::encode_vectors(idx_t n, const float* x, const idx_t* list_nos,
+                                             uint8_t* codes) const {
+    memset(codes, 0, (size_t)n * code_size);
+    std::vector<float> cent, r(d);
+    if (by_residual) {
+        cent.resize((size_t)nlist * d);
+        for (size_t l = 0; l < nlist; l++) quantizer->reconstruct(l, cent.data() + l * d);
+    }
+    for (idx_t i = 0; i < n; i++) {
+        const idx_t l = list_nos[i];
+        if (l < 0) continue;
+        const float* xi = x + (size_t)i * d;
+        if (by_residual) {
+            const float* c = cent.data() + (size_t)l * d;
+            for (int j = 0; j < d; j++) r[j] = xi[j] - c[j];
+            xi = r.data();
+        }
+        sq.compute_codes(xi, codes + (size_t)i * code_size, 1);
+    }
+}
+
+void IndexIVFScalarQuantizer::add_core(idx_t n, const float* x, const idx_t* xids,
+                                       const idx_t* precomputed_idx) {
+    FAISS_THROW_IF_NOT(is_trained);
+    if (!precomputed_idx) {
+        add_with_ids(n, x, xids);
+        return;
+    }
+    for (idx_t i = 0; i < n; i++)
+        FAISS_THROW_IF_NOT_FMT(precomputed_idx[i] < (idx_t)nlist, "Invalid key=%lld nlist=%zd",
+                               (long long)precomputed_idx[i], nlist);
+    std::vector<uint8_t> codes((size_t)n * code_size);
+    encode_vectors(n, x, precomputed_idx, codes.data());
+    for (idx_t i = 0; i < n; i++) {
+        if (precomputed_idx[i] < 0) continue;
+        const idx_t id = xids ? xids[i] : ntotal + i;
+        invlists->add_entries(precomputed_idx[i], 1, &id, codes.data() + (size_t)i * code_size);
+    }
+    ntotal += n;
+    std::lock_guard<std::recursive_mutex> g(mu_);
+    dirty_ = true;
+}
+
+void IndexIVFScalarQuantizer::upload_extra() const {
+    ScalarQuantizer::check_supported((int)sq.qtype, (size_t)d);
+    FAISS_THROW_IF_NOT_MSG(sq.qtype != ScalarQuantizer::QT_8bit || sq.trained.size() == 2 * (size_t)d,
+                           "IndexIVFScalarQuantizer: trained ranges missing");
+    hipStream_t s = stream();
+    const int ldc = ld();
+    std::vector<float> cent((size_t)nlist * ldc, 0.f);
+    for (size_t l = 0; l < nlist; l++) quantizer->reconstruct(l, cent.data() + l * ldc);
+    d_cent_.reserve(sizeof(float) * std::max<size_t>(cent.size(), 1));
+    d_trained_.reserve(sizeof(float) * std::max<size_t>(sq.trained.size(), 1));
+    if (!cent.empty())
+        HIP_CHECK(hipMemcpyAsync(d_cent_.ptr, cent.data(), sizeof(float) * cent.size(),
+                                 hipMemcpyHostToDevice, s));
+    if (!sq.trained.empty())
+        HIP_CHECK(hipMemcpyAsync(d_trained_.ptr, sq.trained.data(),
+                                 sizeof(float) * sq.trained.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // cent is a host temporary
+}
+
+void IndexIVFScalarQuantizer::exact_args(void* p) const {
+    auto& a = *(kern::ExactScanArgs*)p;
+    a.sq.qtype = (int)sq.qtype;
+    a.sq.by_residual = by_residual ? 1 : 0;
+    a.sq.trained = d_trained_.as<float>();
+    a.sq.cent = d_cent_.as<float>();
+    a.sq.ldcent = ld();
+    a.sq.codes = d_codes_.as<uint8_t>();
+    a.sq.cs = device_code_stride();
+}
+
+void IndexIVFScalarQuantizer::search_preassigned_device(idx_t n, const float* x, int ldx, idx_t k,
+                                                        int np, const int32_t* assign,
+                                                        const float* centroid_dis,
+                                                        float* distances, idx_t* labels,
+                                                        hipStream_t s, const uint32_t* lim,
+                                                        const uint8_t* sel,
+                                                        bool store_pairs) const {
+    if (n <= 0) return;
+    sync_device();
+    // IVFSQScannerIP adds the coarse distance of the list when by_residual
+    FAISS_THROW_IF_NOT_MSG(centroid_dis || !(by_residual && metric_type != METRIC_L2),
+                           "IndexIVFScalarQuantizer: inner product by residual needs centroid_dis");
+    exact_scan_device(n, x, ldx, k, np, assign, centroid_dis, distances, labels, s, lim, sel,
+                      store_pairs);
+}
+
+void IndexIVFScalarQuantizer::range_search(idx_t, const float*, float, RangeSearchResult*,
+                                           const SearchParameters*) const {
+    FAISS_THROW_MSG("range_search is not supported on IndexIVFScalarQuantizer");
+}
+
+void IndexIVFScalarQuantizer::range_launch(const float*, idx_t, int, const int32_t*, const float*,
+                                           int, float, const uint8_t*, uint32_t*, const uint64_t*,
+                                           float*, idx_t*, bool, hipStream_t) const {
+    FAISS_THROW_MSG("range search is not supported on IndexIVFScalarQuantizer");
 }
 
 // ---------------------------------------------------------------- shards

@@ -237,6 +237,16 @@ struct ExactPQ {
     const uint8_t* codes = nullptr;  // arena codes
     int cs = 0;                      // code stride (bytes)
 };
+// IVF-SQ side of the exact scan (kernels_sq.hip; arithmetic in sq_ref.h)
+struct ExactSQ {
+    int qtype = -1;                  // ScalarQuantizer::QuantizerType (0 = 8bit, 4 = fp16); < 0: none
+    int by_residual = 1;
+    const float* trained = nullptr;  // vmin [d] | vdiff [d] (8bit)
+    const float* cent = nullptr;     // coarse centroids [nlist][ldcent] fp32
+    int ldcent = 0;
+    const uint8_t* codes = nullptr;  // arena codes
+    int cs = 0;                      // code stride (bytes, multiple of 16)
+};
 struct ExactScanArgs {
     unsigned long long* qdone = nullptr;  // per query completion stamps (search_stats)
     const float* x = nullptr;  // [n][ldx] queries of the chunk
@@ -256,7 +266,12 @@ struct ExactScanArgs {
     const float* codes = nullptr;  // IVF-Flat arena [rows][ldc]
     int ldc = 0;
     ExactPQ pq;  // pq.M > 0: IVF-PQ
+    ExactSQ sq;  // sq.qtype >= 0: IVF-SQ
 };
+// the IVF-SQ candidate pass of ivf_exact_search (between its offsets and its
+// select): keys / rows of every (query, probe) of a at q * cap + eoff[e]
+void ivf_exact_sq_scan(const ExactScanArgs& a, const uint32_t* eoff, int64_t cap, uint32_t* keys,
+                       uint32_t* rows, hipStream_t s);
 // candidates per query (cap) and queries per chunk for a 1 GiB scratch
 int64_t ivf_exact_chunk(int64_t n, int np, uint32_t max_list_len, int64_t* cap_out);
 // eoff [n*np], total [n], keys / rows [n*cap] scratch

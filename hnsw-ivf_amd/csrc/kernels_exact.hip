@@ -6,7 +6,7 @@
 //
 //  1. k_ex_offsets: per query, the candidate offset of each probe
 //     (probe rank order; max_codes prefixes; skipped keys contribute 0).
-//  2. k_ex_flat / k_ex_pq: every candidate row of every probe gets its exact
+//  2. k_ex_flat / k_ex_pq (IVF-SQ: k_ex_sq, kernels_sq.hip): every candidate row of every probe gets its exact
 //     distance in the reference's fp32 order (ref_arith.h, pq_ref.h) and is
 //     stored in arrival order as a 32-bit order-preserving key + its arena row.
 //     Rows outside the IDSelector and distances the reference heap can never
@@ -40,15 +40,7 @@ namespace kern {
 
 namespace {
 
-constexpr uint32_t EX_SKIP = 0xffffffffu;
-
-__device__ __forceinline__ uint32_t ex_key(float dis, bool l2) {
-    if (l2) return dis < FLT_MAX ? ordered_f32(dis) : EX_SKIP;
-    return dis > -FLT_MAX ? ~ordered_f32(dis) : EX_SKIP;
-}
-__device__ __forceinline__ float ex_dis(uint32_t key, bool l2) {
-    return l2 ? unordered_f32(key) : unordered_f32(~key);
-}
+// (EX_SKIP / ex_key / ex_dis: wave_select.h, shared with kernels_sq.hip)
 
 // ---------------------------------------------------------------- offsets
 __global__ __launch_bounds__(256) void k_ex_offsets(const int32_t* __restrict__ assign, int64_t n,
@@ -463,7 +455,9 @@ void ivf_exact_search(const ExactScanArgs& a, uint32_t* eoff, uint32_t* total, u
     HIP_LAUNCH_CHECK();
     const int64_t entries = a.n * (int64_t)a.np;
     FAISS_THROW_IF_NOT(entries < ((int64_t)1 << 31));
-    if (a.pq.M > 0) {
+    if (a.sq.qtype >= 0) {
+        ivf_exact_sq_scan(a, eoff, cap, keys, rows, s);
+    } else if (a.pq.M > 0) {
         const size_t lds = sizeof(float) * ((size_t)a.pq.M * 256 + 2 * (size_t)a.ldx + 1);
         FAISS_THROW_IF_NOT_FMT(lds <= 160 * 1024, "IVF-PQ table of M = %d does not fit in LDS",
                                a.pq.M);

@@ -56,6 +56,9 @@ struct SDevGuard {
 size_t ivf_copy_subset_to(const IndexIVF* src, IndexIVF* dst, int subset_type, idx_t a1,
                           idx_t a2) {
     FAISS_THROW_IF_NOT(src && dst && src != dst);
+    FAISS_THROW_IF_NOT_MSG(!dynamic_cast<const IndexIVFScalarQuantizer*>(src) &&
+                                   !dynamic_cast<const IndexIVFScalarQuantizer*>(dst),
+                           "copy_subset_to is not supported on IndexIVFScalarQuantizer");
     const ArrayInvertedLists& il = *src->invlists;
     ArrayInvertedLists& ol = *dst->invlists;
     FAISS_THROW_IF_NOT(il.nlist == ol.nlist);
@@ -175,6 +178,8 @@ IndexIVF* clone_empty(const IndexIVF* src, int device) {
 IndexShardsIVF* index_ivf_to_shards(const IndexIVF* src, int nshard, int shard_type,
                                     const int* devices) {
     FAISS_THROW_IF_NOT(src && nshard >= 1);
+    FAISS_THROW_IF_NOT_MSG(!dynamic_cast<const IndexIVFScalarQuantizer*>(src),
+                           "index_ivf_to_shards is not supported on IndexIVFScalarQuantizer");
     FAISS_THROW_IF_NOT_FMT(shard_type == 1 || shard_type == 2 || shard_type == 4,
                            "shard_type %d not implemented", shard_type);
     std::vector<IndexIVF*> sh;
@@ -416,6 +421,8 @@ IndexShardsIVF::IndexShardsIVF(Index* q, size_t nl, bool th, bool succ)
 
 void IndexShardsIVF::add_shard(IndexIVF* idx) {
     FAISS_THROW_IF_NOT(idx && idx->d == d && idx->nlist == nlist);
+    FAISS_THROW_IF_NOT_MSG(!dynamic_cast<const IndexIVFScalarQuantizer*>(idx),
+                           "IndexShardsIVF does not support IndexIVFScalarQuantizer shards");
     // shards on other devices are searched over RCCL (shards.cpp)
     shards.push_back(idx);
     md_.reset();

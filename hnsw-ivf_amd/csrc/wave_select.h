@@ -162,6 +162,19 @@ __device__ __forceinline__ float unordered_f32(uint32_t u) {
     return __uint_as_float(u ^ (~(uint32_t)((int32_t)u >> 31) | 0x80000000u));
 }
 
+// Candidate key of the general exact scan (kernels_exact.hip, kernels_sq.hip):
+// ascending key = the reference heap's preference (L2 smaller, IP larger);
+// EX_SKIP for what the heap can never admit (!(dis < FLT_MAX) for L2,
+// !(dis > -FLT_MAX) for IP, NaN) and for rows outside the IDSelector.
+constexpr uint32_t EX_SKIP = 0xffffffffu;
+__device__ __forceinline__ uint32_t ex_key(float dis, bool l2) {
+    if (l2) return dis < FLT_MAX ? ordered_f32(dis) : EX_SKIP;
+    return dis > -FLT_MAX ? ~ordered_f32(dis) : EX_SKIP;
+}
+__device__ __forceinline__ float ex_dis(uint32_t key, bool l2) {
+    return l2 ? unordered_f32(key) : unordered_f32(~key);
+}
+
 template <int KQ>
 struct ThreadQueue {
     unsigned long long q[KQ];

@@ -78,6 +78,10 @@ using faiss_amd::IndexIVFFlat;
 using faiss_amd::IndexIVFPQ;
 using faiss_amd::ProductQuantizer;
 
+// faiss/IndexScalarQuantizer.h (the IVF class only), faiss/impl/ScalarQuantizer.h
+using faiss_amd::IndexIVFScalarQuantizer;
+using faiss_amd::ScalarQuantizer;
+
 // faiss/IndexShardsIVF.h
 using faiss_amd::IndexShardsIVF;
 

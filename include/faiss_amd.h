@@ -2,7 +2,7 @@
 //
 // Mirrors the reference faiss::Index hierarchy for the hot path
 // (faiss/Index.h:108-181, faiss/IndexFlat.h, faiss/IndexIVF.h:39-587,
-// faiss/IndexIVFFlat.h, faiss/IndexIVFPQ.h, faiss/IndexHNSW.h,
+// faiss/IndexIVFFlat.h, faiss/IndexIVFPQ.h, faiss/IndexScalarQuantizer.h, faiss/IndexHNSW.h,
 // faiss/IndexShardsIVF.h): same class names, method signatures, argument
 // meaning and exceptions, in namespace faiss_amd.  Indexes are GPU-resident:
 // host mirrors keep the faiss data structures (for I/O and reconstruction),
@@ -794,6 +794,72 @@ struct IndexIVFPQ : IndexIVF {
     mutable bool pq_stream_ready_ = false;
 };
 
+// faiss/impl/ScalarQuantizer.h:26-98.  QT_8bit and QT_fp16 with d % 8 == 0 are
+// served (the reference's 8-wide path, csrc/sq_ref.h); anything else throws.
+struct ScalarQuantizer {
+    enum QuantizerType {
+        QT_8bit,
+        QT_4bit,
+        QT_8bit_uniform,
+        QT_4bit_uniform,
+        QT_fp16,
+        QT_8bit_direct,
+        QT_6bit,
+        QT_bf16,
+        QT_8bit_direct_signed,
+    };
+    enum RangeStat { RS_minmax, RS_meanstd, RS_quantiles, RS_optim };
+    QuantizerType qtype = QT_8bit;
+    RangeStat rangestat = RS_minmax;
+    float rangestat_arg = 0;
+    size_t d = 0, code_size = 0;
+    size_t bits = 0;             // per component
+    std::vector<float> trained;  // QT_8bit: vmin [d] | vdiff [d]; QT_fp16: empty
+    ScalarQuantizer() = default;
+    ScalarQuantizer(size_t d, QuantizerType qtype);
+    void set_derived_sizes();
+    // throws a FaissException naming the qtype / d unless served
+    static void check_supported(int qtype, size_t d);
+    static const char* qtype_name(int qtype);
+    // train_NonUniform with RS_minmax (ScalarQuantizer.cpp:1086-1115) on all n
+    // vectors: the reference subsamples above 100 000 training vectors
+    // (train_encoder_num_vectors), so ranges equal its only for n <= 100 000
+    void train(size_t n, const float* x);
+    void compute_codes(const float* x, uint8_t* codes, size_t n) const;
+    void decode(const uint8_t* codes, float* x, size_t n) const;
+};
+
+// faiss/IndexScalarQuantizer.h:65-125
+struct IndexIVFScalarQuantizer : IndexIVF {
+    ScalarQuantizer sq;
+    IndexIVFScalarQuantizer(Index* quantizer, size_t d, size_t nlist,
+                            ScalarQuantizer::QuantizerType qtype, MetricType metric = METRIC_L2,
+                            bool by_residual = true);
+    void train_encoder(idx_t n, const float* x, const idx_t* assign) override;
+    void encode_vectors(idx_t n, const float* x, const idx_t* list_nos,
+                        uint8_t* codes) const override;
+    void search_preassigned_device(idx_t n, const float* x, int ldx, idx_t k, int nprobe,
+                                   const int32_t* assign, const float* centroid_dis,
+                                   float* distances, idx_t* labels, hipStream_t stream,
+                                   const uint32_t* lim = nullptr, const uint8_t* sel = nullptr,
+                                   bool store_pairs = false) const override;
+    // faiss/IndexScalarQuantizer.cpp:207-260: add to the lists precomputed_idx
+    // names (nullptr: the quantizer assigns; < 0: not stored)
+    void add_core(idx_t n, const float* x, const idx_t* xids, const idx_t* precomputed_idx);
+    // not offered on this index type: throws, naming it
+    void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result,
+                      const SearchParameters* params = nullptr) const override;
+
+   protected:
+    void upload_extra() const override;
+    void exact_args(void* args) const override;
+    void range_launch(const float* x, idx_t n, int ldx, const int32_t* assign, const float* cdis,
+                      int np, float radius, const uint8_t* sel, uint32_t* counts,
+                      const uint64_t* offs, float* D, idx_t* I, bool store_pairs,
+                      hipStream_t s) const override;
+    mutable DeviceBuffer d_trained_, d_cent_;
+};
+
 // ---------------------------------------------------------------- shards
 // faiss/IndexShardsIVF.h:19-40 — shards sharing one coarse quantizer.
 struct IndexShardsIVF : Index {
@@ -885,7 +951,7 @@ Index* read_index(const char* fname, int io_flags = 0);
 void write_index_ondisk(const Index* idx, const char* fname, const char* lists_fname);
 Index* read_index(FILE* f, int io_flags = 0);
 
-// faiss/index_factory.h (subset: Flat, IVFn[_HNSWm],Flat|PQm[xb][np], HNSWm)
+// faiss/index_factory.h (subset: Flat, IVFn[_HNSWm],Flat|PQm[xb][np]|SQ8|SQfp16, HNSWm)
 Index* index_factory(int d, const char* description, MetricType metric = METRIC_L2);
 
 // The reference's IndexIVF::search cuts a batch into min(omp threads, n)

@@ -343,6 +343,74 @@ int faiss_amd_IndexIVFPQ_info(
  * arithmetic of the GPU re-rank.  0 is always valid, 1 needs by_residual L2 */
 int faiss_amd_IndexIVFPQ_set_use_precomputed_table(FaissIndexIVFPQ* index, int v);
 
+/* ---------------- IndexIVFScalarQuantizer (c_api/IndexScalarQuantizer_c.h) -
+ * The IVF declarations of that header (:51 to its end).  QT_8bit and QT_fp16
+ * with d % 8 == 0 are served; a constructor given anything else returns -2
+ * with the qtype / d in faiss_get_last_error().  The non-IVF
+ * IndexScalarQuantizer functions (:36-49) are not declared: a caller of those
+ * fails to compile rather than at run time. */
+/* IndexScalarQuantizer_c.h:20-31 */
+typedef enum FaissQuantizerType {
+    QT_8bit,
+    QT_4bit,
+    QT_8bit_uniform,
+    QT_4bit_uniform,
+    QT_fp16,
+    QT_8bit_direct,
+    QT_6bit,
+    QT_bf16,
+    QT_8bit_direct_signed,
+} FaissQuantizerType;
+typedef struct FaissIndex_H FaissIndexIVFScalarQuantizer;
+/* :54-56 */
+FaissIndexIVFScalarQuantizer* faiss_IndexIVFScalarQuantizer_cast(FaissIndex* index);
+void faiss_IndexIVFScalarQuantizer_free(FaissIndexIVFScalarQuantizer* obj);
+/* :58: an empty QT_8bit index of d = 0 (by_residual true) that owns a flat
+ * quantizer, as faiss_IndexIVFFlat_new gives */
+int faiss_IndexIVFScalarQuantizer_new(FaissIndexIVFScalarQuantizer** p_index);
+/* :60-65 (L2, by residual) */
+int faiss_IndexIVFScalarQuantizer_new_with(
+        FaissIndexIVFScalarQuantizer** p_index,
+        FaissIndex* quantizer,
+        idx_t d,
+        size_t nlist,
+        FaissQuantizerType qt);
+/* :67-74 */
+int faiss_IndexIVFScalarQuantizer_new_with_metric(
+        FaissIndexIVFScalarQuantizer** p_index,
+        FaissIndex* quantizer,
+        size_t d,
+        size_t nlist,
+        FaissQuantizerType qt,
+        FaissMetricType metric,
+        int encode_residual);
+/* :76-84 */
+size_t faiss_IndexIVFScalarQuantizer_nlist(const FaissIndexIVFScalarQuantizer*);
+size_t faiss_IndexIVFScalarQuantizer_nprobe(const FaissIndexIVFScalarQuantizer*);
+void faiss_IndexIVFScalarQuantizer_set_nprobe(FaissIndexIVFScalarQuantizer*, size_t);
+FaissIndex* faiss_IndexIVFScalarQuantizer_quantizer(const FaissIndexIVFScalarQuantizer*);
+int faiss_IndexIVFScalarQuantizer_own_fields(const FaissIndexIVFScalarQuantizer*);
+void faiss_IndexIVFScalarQuantizer_set_own_fields(FaissIndexIVFScalarQuantizer*, int);
+/* :86-91 (IndexIVFScalarQuantizer::add_core): add n vectors with ids xids
+ * (NULL: ntotal, ntotal + 1, ...) to the lists precomputed_idx names (NULL:
+ * the quantizer assigns them; < 0: the vector is not stored) */
+int faiss_IndexIVFScalarQuantizer_add_core(
+        FaissIndexIVFScalarQuantizer* index,
+        idx_t n,
+        const float* x,
+        const idx_t* xids,
+        const idx_t* precomputed_idx);
+/* extensions: qtype, by_residual and the ScalarQuantizer's trained vector
+ * (host pointer, *p_size floats: vmin [d] | vdiff [d] for QT_8bit, 0 for QT_fp16) */
+int faiss_amd_IndexIVFScalarQuantizer_info(
+        const FaissIndexIVFScalarQuantizer* index,
+        int* qtype,
+        int* by_residual);
+int faiss_amd_IndexIVFScalarQuantizer_trained(
+        const FaissIndexIVFScalarQuantizer* index,
+        const float** p_trained,
+        size_t* p_size);
+
 /* ---------------- IndexHNSWFlat (C++ faiss/IndexHNSW.h:IndexHNSWFlat) ---- */
 int faiss_amd_IndexHNSWFlat_new_with(
         FaissIndexHNSW** p_index,
@@ -519,7 +587,8 @@ int faiss_amd_merge_knn_results(
         FaissMetricType metric);
 
 /* extension: dynamic type of a handle ("IndexFlat", "IndexIVFFlat",
- * "IndexIVFPQ", "IndexHNSWFlat", "IndexShardsIVF", "Index") */
+ * "IndexIVFPQ", "IndexIVFScalarQuantizer", "IndexHNSWFlat", "IndexShardsIVF",
+ * "Index") */
 const char* faiss_amd_Index_type(const FaissIndex* index);
 
 /* ---------------- device-resident extensions (no reference counterpart) */
