@@ -1416,9 +1416,9 @@ void IndexIVFFlat::search_preassigned_device(idx_t n, const float* x, int ldx, i
     }
     flip_counts();
     const bool l2 = metric_type == METRIC_L2;
-    s_flags_.reserve(sizeof(uint32_t) * std::max<idx_t>(n, 4));
+    s_flags_.reserve(sizeof(uint32_t) * std::max<idx_t>(n, 5));
     const bool dbg = getenv("FAISS_AMD_IVF_STATS") != nullptr;
-    if (dbg) HIP_CHECK(hipMemsetAsync(s_flags_.ptr, 0, 4 * sizeof(uint32_t), s));
+    if (dbg) HIP_CHECK(hipMemsetAsync(s_flags_.ptr, 0, 5 * sizeof(uint32_t), s));
     // query image + |x|^2: the quantizer's when this is search()'s chunk
     const void* qready = shared_qimg_;
     if (!qready) s_q_.reserve(kern::query_image_bytes(n, d) + sizeof(float) * n);
@@ -1432,13 +1432,14 @@ void IndexIVFFlat::search_preassigned_device(idx_t n, const float* x, int ldx, i
                              qready ? const_cast<void*>(qready) : s_q_.ptr, qready != nullptr,
                              qdone_, fold_, ktm);
     if (dbg) {
-        uint32_t st[4];
+        uint32_t st[5];
         HIP_CHECK(hipMemcpyAsync(st, s_flags_.ptr, sizeof(st), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         fprintf(stderr,
-                "[faiss_amd] ivf mfma scan: nq=%lld survivors/q=%.2f failing probes/q=%.4f "
-                "overflow queries=%u general-resolve queries=%u\n",
-                (long long)n, st[0] / (double)n, st[1] / (double)n, st[2], st[3]);
+                "[faiss_amd] ivf mfma scan: nq=%lld survivors/q=%.2f exact rows/q=%.2f "
+                "failing probes/q=%.4f overflow queries=%u general-resolve queries=%u\n",
+                (long long)n, st[0] / (double)n, st[4] / (double)n, st[1] / (double)n, st[2],
+                st[3]);
     }
 }
 
@@ -1739,8 +1740,8 @@ void IndexIVFPQ::search_preassigned_device(idx_t n, const float* x, int ldx, idx
         }
         flip_counts();
         const bool dbg = getenv("FAISS_AMD_IVF_STATS") != nullptr;
-        s_pflags_.reserve(4 * sizeof(uint32_t));
-        if (dbg) HIP_CHECK(hipMemsetAsync(s_pflags_.ptr, 0, 4 * sizeof(uint32_t), s));
+        s_pflags_.reserve(5 * sizeof(uint32_t));
+        if (dbg) HIP_CHECK(hipMemsetAsync(s_pflags_.ptr, 0, 5 * sizeof(uint32_t), s));
         int KT = 0;
         // query image: the flat quantizer's when this is search()'s chunk,
         // else prepared here (one launch instead of a split per work item)
@@ -1786,13 +1787,14 @@ void IndexIVFPQ::search_preassigned_device(idx_t n, const float* x, int ldx, idx
                                pq_fold ? 1 : 0);
         }
         if (dbg) {
-            uint32_t st[4];
+            uint32_t st[5];
             HIP_CHECK(hipMemcpyAsync(st, s_pflags_.ptr, sizeof(st), hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
             fprintf(stderr,
-                    "[faiss_amd] ivfpq mfma scan: nq=%lld survivors/q=%.2f failing streams/q=%.4f "
-                    "overflow queries=%u general-resolve queries=%u\n",
-                    (long long)n, st[0] / (double)n, st[1] / (double)n, st[2], st[3]);
+                    "[faiss_amd] ivfpq mfma scan: nq=%lld survivors/q=%.2f exact rows/q=%.2f "
+                    "failing streams/q=%.4f overflow queries=%u general-resolve queries=%u\n",
+                    (long long)n, st[0] / (double)n, st[4] / (double)n, st[1] / (double)n, st[2],
+                    st[3]);
         }
         return;
     }

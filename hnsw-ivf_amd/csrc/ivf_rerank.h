@@ -63,11 +63,15 @@ namespace kern {
 //      (dropped bound, largest margin M, arena offset / length) and the
 //      query, all independent;  ub' = approx_hi + M and lb' = approx_lo - M
 //      bracket each entry's exact key (M >= the entry's own margin);
-//   2. the survivors' rows and ids.
+//   2. the survivors' rows and ids.  The Flat evaluator fetches them in two
+//      rounds (below: the 16 with the smallest ub' first, then only those
+//      whose lb' is <= the k-th exact key of the first round), which reads
+//      about a third fewer rows than the sweep over every lb' <= U.
 // Invalid / empty probes carry empty entries (k_bucket_fill), so neither the
 // assignment nor the list geometry arrays are read.
 // Exact distances: 4 lanes per row (ref_arith.h order, see eval_rows64_direct).
 constexpr int RR_CAP = 512;
+constexpr int RR2_CAP = 256;  // most candidates of a two-round query (4 batches)
 constexpr int RR_XM = BDM / 8;
 constexpr int RR_W = 1;  // waves (queries) per block: one, for fine-grained packing
 // (the re-rank's barriers sit in wave-uniform branches: one wave per block)
@@ -82,6 +86,13 @@ static_assert(RR_W == 1, "k_ivf_rerank assumes one wave per block");
 #ifndef RR_PB
 #define RR_PB 1
 #endif
+// set bits of the wave mask m below this lane (v_mbcnt: no per-lane 64-bit
+// mask to keep in registers)
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                          __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
 template <bool L2>
 __device__ __forceinline__ float eval_rows64_direct(const float* xr, const float* __restrict__ xq,
                                                     const float* __restrict__ codes, int ldc,
@@ -363,14 +374,18 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
     const uint32_t lfail = __shfl(my_fail, lp);
     // ---- candidates -> LDS as arena rows: kept entries with lb' <= U of the
     // streams that did not fail, then every row of the failing streams
+    // (Flat: the first RR2_CAP candidates' brackets lb' / ub' go to the LDS
+    // beside them, for the two-round evaluation below)
     int ns = 0;
 #pragma unroll
     for (int i = 0; i < V; i++) {
         const int sl = ((lane * V + i) % KE) / KT;
         bool sv = false;
         uint32_t grow = 0;
+        float lbv = 0.f;
         if (kv[i] != 0xffffffffu && !((lfail >> sl) & 1u)) {
-            sv = ivf_decode_lo<L2>(kv[i], lowmask, fold) - lm <= U;
+            lbv = ivf_decode_lo<L2>(kv[i], lowmask, fold) - lm;
+            sv = lbv <= U;
             grow = loff + ivf_key_row(kv[i], lowmask, sl);
         }
         const unsigned long long m = __ballot(sv);
@@ -378,6 +393,12 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
         if (sv && pos < RR_CAP) {
             surv[w][pos] = grow;
             sprobe[w][pos] = (uint16_t)lp;
+            if constexpr (PQD == 0) {
+                if (pos < RR2_CAP) {
+                    stg[w][pos] = lbv;
+                    stg[w][RR2_CAP + pos] = ub[i];
+                }
+            }
         }
         ns += __popcll(m);
     }
@@ -441,59 +462,193 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
     unsigned long long t_e = 0ull;
     auto small = [&](auto nbc) {
         constexpr int NB = decltype(nbc)::value;
+        if constexpr (NB == 1) {
+            const bool ok = lane < ns;
+            float k1[1];
+            long long k2[1];
+            st.emit(ok, ok ? surv[w][lane] : 0u, ok ? (int)sprobe[w][lane] : 0, k1[0], k2[0],
+                    max(0, min(64, ns)));
+            if (!(ok && key_admissible(k1[0]))) {
+                k1[0] = WS_INF;
+                k2[0] = WS_NOID;
+            }
+            t_e = trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
+            return exact_topk_small<1>(k1, k2, ns, k, L2 ? 1 : 0, lane, valid, D + q * k,
+                                       I + q * k);
+        } else {
+            // only keys <= U can be in the top k (at least k kept entries have
+            // exact keys <= their ub' <= U; boundary ties are <= U too): each
+            // batch's keys <= U go straight to the LDS, in order (failing
+            // streams add whole slots of rows, most of them far above U), so
+            // no batch's keys wait in registers while the next one's rows load
+            float* ck1 = stg[w];
+            long long* ck2 = reinterpret_cast<long long*>(stg[w] + 64 * NB);
+            int m = 0;
+#pragma unroll
+            for (int b = 0; b < NB; b++) {
+                const bool ok = 64 * b + lane < ns;
+                float a1;
+                long long a2;
+                st.emit(ok, ok ? surv[w][64 * b + lane] : 0u,
+                        ok ? (int)sprobe[w][64 * b + lane] : 0, a1, a2,
+                        max(0, min(64, ns - 64 * b)));
+                const bool in = ok && key_admissible(a1) && a1 <= U;
+                const unsigned long long bm = __ballot(in);
+                const int pos = m + lanes_below(bm);
+                if (in) {
+                    ck1[pos] = a1;
+                    ck2[pos] = a2;
+                }
+                m += __popcll(bm);
+            }
+            t_e = trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
+            __syncthreads();  // one wave per block
+            if (m <= 64) {
+                float c1[1] = {lane < m ? ck1[lane] : WS_INF};
+                long long c2[1] = {lane < m ? ck2[lane] : WS_NOID};
+                return exact_topk_small<1>(c1, c2, m, k, L2 ? 1 : 0, lane, valid, D + q * k,
+                                           I + q * k);
+            }
+            float k1[NB];
+            long long k2[NB];
+#pragma unroll
+            for (int b = 0; b < NB; b++) {
+                const bool has = 64 * b + lane < m;
+                k1[b] = has ? ck1[64 * b + lane] : WS_INF;
+                k2[b] = has ? ck2[64 * b + lane] : WS_NOID;
+            }
+            return exact_topk_small<NB>(k1, k2, m, k, L2 ? 1 : 0, lane, valid, D + q * k,
+                                        I + q * k);
+        }
+    };
+    // ---- Flat, common path (no failing stream, P < ns <= RR2_CAP): two
+    // rounds.  A = the P = 16 ceil(k / 16) candidates with the smallest ub'
+    // (one pass of 16 rows for k <= 16); T = the k-th smallest admissible
+    // exact key of A, an upper bound of the exact k-th key of the whole stream
+    // (every member of A is a candidate) that is <= U when A holds the k
+    // smallest ub'.  B = the other candidates with lb' <= T: a top-k member
+    // (boundary ties included) has lb' <= exact <= the exact k-th key <= T.
+    // The window above the k-th approximation shrinks from 2 M to about M
+    // (c2: 34.8 -> 22.3 rows per query).  With fewer than k admissible
+    // keys in A every candidate is evaluated.  The A u B keys are ranked as
+    // the single sweep's are; a boundary tie goes to exact_topk_resolve over
+    // the whole candidate list (surv[] is left as it was).
+    int nrows = min(ns, RR_CAP);  // rows evaluated exactly (stats, trace)
+    unsigned long long t_a = 0ull;
+    auto two_round = [&](auto nbc, int P) {
+        constexpr int NB = decltype(nbc)::value;
+        const float* lbs = stg[w];
+        const float* ubs = stg[w] + RR2_CAP;
+        uint16_t* ordb = reinterpret_cast<uint16_t*>(stg[w] + 2 * RR2_CAP);  // RR2_CAP
+        uint16_t* orda = ordb + RR2_CAP;                                    // 64
+        float uv[NB];
+#pragma unroll
+        for (int b = 0; b < NB; b++) uv[b] = 64 * b + lane < ns ? ubs[64 * b + lane] : WS_INF;
+        // (an upper bound of the P-th smallest ub': the first P in position
+        // order of the values under it; any subset of the candidates serves)
+        const float ts = wave_kth_smallest<NB, 8>(uv, P);
+        bool ina[NB];
+        int na = 0;
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            const bool in = 64 * b + lane < ns && uv[b] <= ts;
+            const unsigned long long m = __ballot(in);
+            const int pos = na + lanes_below(m);
+            ina[b] = in && pos < P;
+            if (ina[b]) orda[pos] = (uint16_t)(64 * b + lane);
+            na += __popcll(m);
+        }
+        na = min(na, P);
+        __syncthreads();  // one wave per block
+        const bool oka = lane < na;
+        const int ca = oka ? (int)orda[lane] : 0;
+        float a1;
+        long long a2;
+        st.emit(oka, oka ? surv[w][ca] : 0u, oka ? (int)sprobe[w][ca] : 0, a1, a2, na);
+        if (!(oka && key_admissible(a1))) {
+            a1 = WS_INF;
+            a2 = WS_NOID;
+        }
+        t_a = trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
+        const float av[1] = {a1};
+        float T = wave_kth_smallest<1, 8>(av, k);  // (an upper bound within 2^-15)
+        const bool all = !(T < WS_INF);             // fewer than k admissible keys
+        T = fminf(T, U);                            // (both bound the exact k-th key)
+        int nb = 0;
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            const int c = 64 * b + lane;
+            const bool in = c < ns && !ina[b] && (all || lbs[c] <= T);
+            const unsigned long long m = __ballot(in);
+            if (in) ordb[nb + lanes_below(m)] = (uint16_t)c;
+            nb += __popcll(m);
+        }
+        __syncthreads();
+        const int m = na + nb;  // <= ns: A and B are disjoint
+        nrows = m;
+        // A's keys wait in the LDS (the brackets are done with) while B's rows
+        // are evaluated, and follow B's: positions nb .. nb + na - 1
+        float* sa1 = stg[w];
+        long long* sa2 = reinterpret_cast<long long*>(stg[w] + 64);
+        if (oka) {
+            sa1[lane] = a1;
+            sa2[lane] = a2;
+        }
         float k1[NB];
         long long k2[NB];
 #pragma unroll
         for (int b = 0; b < NB; b++) {
-            const bool ok = 64 * b + lane < ns;
-            st.emit(ok, ok ? surv[w][64 * b + lane] : 0u, ok ? (int)sprobe[w][64 * b + lane] : 0,
-                    k1[b], k2[b], max(0, min(64, ns - 64 * b)));
+            const bool ok = 64 * b + lane < nb;
+            const int c = ok ? (int)ordb[64 * b + lane] : 0;
+            st.emit(ok, ok ? surv[w][c] : 0u, ok ? (int)sprobe[w][c] : 0, k1[b], k2[b],
+                    max(0, min(64, nb - 64 * b)));
             if (!(ok && key_admissible(k1[b]))) {
                 k1[b] = WS_INF;
                 k2[b] = WS_NOID;
             }
         }
         t_e = trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
-        if constexpr (NB > 1) {
-            // only keys <= U can be in the top k (at least k kept entries have
-            // exact keys <= their ub' <= U; boundary ties are <= U too): the
-            // order-preserving compaction of those (failing streams add whole
-            // slots of rows, most of them far above U) ranks in one batch
-            float* ck1 = stg[w];
-            long long* ck2 = reinterpret_cast<long long*>(stg[w] + 64 * NB);
-            int m = 0;
+        __syncthreads();
 #pragma unroll
-            for (int b = 0; b < NB; b++) {
-                const bool in = 64 * b + lane < ns && k1[b] < WS_INF && k1[b] <= U;
-                const unsigned long long bm = __ballot(in);
-                const int pos = m + __popcll(bm & ((1ull << lane) - 1ull));
-                if (in) {
-                    ck1[pos] = k1[b];
-                    ck2[pos] = k2[b];
-                }
-                m += __popcll(bm);
+        for (int b = 0; b < NB; b++) {
+            const int j = 64 * b + lane;
+            if (j >= nb && j < m) {
+                k1[b] = sa1[j - nb];
+                k2[b] = sa2[j - nb];
             }
+        }
+        if constexpr (NB > 1) {
             if (m <= 64) {
-                __syncthreads();  // one wave per block
-                float c1[1] = {lane < m ? ck1[lane] : WS_INF};
-                long long c2[1] = {lane < m ? ck2[lane] : WS_NOID};
-                __syncthreads();
+                float c1[1] = {k1[0]};
+                long long c2[1] = {k2[0]};
                 return exact_topk_small<1>(c1, c2, m, k, L2 ? 1 : 0, lane, valid, D + q * k,
                                            I + q * k);
             }
         }
-        return exact_topk_small<NB>(k1, k2, ns, k, L2 ? 1 : 0, lane, valid, D + q * k,
-                                    I + q * k);
+        return exact_topk_small<NB>(k1, k2, m, k, L2 ? 1 : 0, lane, valid, D + q * k, I + q * k);
     };
-    if (ns <= 64) done = small(std::integral_constant<int, 1>());
-    else if (ns <= 128) done = small(std::integral_constant<int, 2>());
-    else if (ns <= 256) done = small(std::integral_constant<int, 4>());
+    bool two = false;
+    if constexpr (PQD == 0) {
+        const int P = 16 * ((k + 15) >> 4);
+        two = fmask == 0ull && P <= 64 && ns > P && ns <= RR2_CAP;
+        if (two) {
+            if (ns <= 64) done = two_round(std::integral_constant<int, 1>(), P);
+            else if (ns <= 128) done = two_round(std::integral_constant<int, 2>(), P);
+            else done = two_round(std::integral_constant<int, 4>(), P);
+        }
+    }
+    if (!two) {
+        if (ns <= 64) done = small(std::integral_constant<int, 1>());
+        else if (ns <= 128) done = small(std::integral_constant<int, 2>());
+        else if (ns <= 256) done = small(std::integral_constant<int, 4>());
+    }
     if (!done) exact_topk_resolve(st, k, L2 ? 1 : 0, lane, valid, D + q * k, I + q * k);
     if (stats && valid && lane == 0) {
         atomicAdd(&stats[0], (uint32_t)min(nkept, RR_CAP));
         atomicAdd(&stats[1], (uint32_t)__popcll(fmask));
         atomicAdd(&stats[2], st.overflow ? 1u : 0u);
         atomicAdd(&stats[3], done ? 0u : 1u);
+        atomicAdd(&stats[4], (uint32_t)nrows);
     }
     // search_stats: the query's completion on the device clock
     if (qdone && valid && lane == 0) qdone[q] = __builtin_amdgcn_s_memrealtime();
@@ -505,6 +660,8 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
         trace[8 * q + 3] = t_u;
         trace[8 * q + 4] = t_c;
         trace[8 * q + 5] = t_e;
+        trace[8 * q + 6] = t_a;  // after round A (0: single sweep)
+        trace[8 * q + 7] = (unsigned long long)nrows;
     }
 }
 
@@ -849,6 +1006,7 @@ __global__ __launch_bounds__(64, RR_WAVES) void k_ivf_rerank_wide(
         atomicAdd(&stats[1], (uint32_t)nfail);
         atomicAdd(&stats[2], st.overflow ? 1u : 0u);
         atomicAdd(&stats[3], done ? 0u : 1u);
+        atomicAdd(&stats[4], (uint32_t)min(ns, RR_CAP));  // rows evaluated exactly
     }
     if (qdone && lane == 0) qdone[q] = __builtin_amdgcn_s_memrealtime();
 }

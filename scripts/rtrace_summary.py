@@ -1,6 +1,7 @@
 """Summarise a re-rank trace (FAISS_AMD_RERANK_TRACE=<file>): per query
 s_memrealtime (100 MHz) stamps: start, end, ns | fails << 32, after U, after
-the candidate list, after the exact evaluation."""
+the candidate list, after the exact evaluation, after round A of a two-round
+query (0: single sweep), rows evaluated exactly."""
 import sys
 
 import numpy as np
@@ -14,8 +15,13 @@ ph = {"round trip 1 + U": a[:, 3] - a[:, 0], "candidates": a[:, 4] - a[:, 3],
       "total": a[:, 1] - a[:, 0]}
 print(f"queries {len(a)} span {(a[:, 1].max() - a[:, 0].min()) * us:.1f} us; "
       f"survivors mean {(a[:, 2] & 0xffffffff).mean():.1f}")
+two = (a[:, 6] > 0) & (a[:, 5] > 0)
+if two.any():
+    ph["  round A (two-round queries)"] = np.where(two, a[:, 6] - a[:, 4], 0)
+    ph["  T + round B"] = np.where(two, a[:, 5] - a[:, 6], 0)
+    print(f"two-round queries {two.sum()}; exact rows mean {a[:, 7].mean():.1f}")
 for k, v in ph.items():
-    v = v[a[:, 5] > 0] * us
+    v = v[(a[:, 5] > 0) & (two if k.startswith("  ") else True)] * us
     print(f"  {k:28s} mean {v.mean():6.2f} p50 {np.median(v):6.2f} p95 {np.percentile(v, 95):6.2f} us")
 end = np.sort(a[:, 1] - a[:, 0].min()) * us
 print("  in flight (mean over span):", f"{((a[:, 1] - a[:, 0]).sum() * us) / (end[-1]):.0f}")
