@@ -332,7 +332,9 @@ __global__ __launch_bounds__(256, Y3 ? 2 : 3) void k_ivf_bf3_filter(
 // code: bf16(code) hi part, then the row's fp32 norm (+inf for padding rows)
 // and 12 zero bytes (split_bf16_stream).  Lists are aligned to BV rows, so a
 // tile never leaves its list: padding rows' keys sort after every real
-// candidate and the epilogue drops them by row index.  The LDS image is the
+// candidate and the epilogue drops them by row index (PIPE form; the
+// sequential form does not copy or compute the last tile's padding, see
+// nv_last).  The LDS image is the
 // rows back to back (glds writes 1 KB blocks linearly); the 16-B tail makes
 // the row stride 4 banks mod 64, so the 16 rows of a ds_read_b128 quarter
 // hit distinct banks without a swizzle.
@@ -393,7 +395,10 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_ivf_bf2_stream(
     // vmcnt(0) before the tile reads): the 2 tile buffers
     __shared__ __attribute__((aligned(16))) uint8_t smem[NB * TB];
     uint8_t* tiles = smem;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x, lane = t & 63;
+    // (sequential form: the wave index as a scalar, so that the tile copy's
+    // block tests and addresses are scalar arithmetic)
+    const int w = PIPE ? t >> 6 : __builtin_amdgcn_readfirstlane(t >> 6);
     const uint32_t xcd = blockIdx.x & 7u, rest = blockIdx.x >> 3;
     const uint32_t item = 4u * ((rest >> 2) * 8u + xcd) + (rest & 3u);
     const uint32_t nitems = item_off[nlist];
@@ -412,14 +417,15 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_ivf_bf2_stream(
     const bool qvalid = qloc < nQ;
 
     // glds of tile j into buffer b: the tile's rows are contiguous in the
-    // stream image and in LDS; wave w copies 1 KB blocks w, w + 4, ...
-    auto issue = [&](int j, int b) {
+    // stream image and in LDS; wave w copies 1 KB blocks w, w + 4, ... below
+    // nblk (NG: the whole tile)
+    auto issue = [&](int j, int b, int nblk) {
         const uint8_t* src = cbs + (row0 + (int64_t)j * BV) * SR + 16 * lane;
         uint8_t* dst = tiles + b * TB;
 #pragma unroll
         for (int g = 0; g < G0; g++) {
             const int blk = w + 4 * g;
-            if (g < G3 || blk < NG)  // wave-uniform
+            if ((g < G3 || blk < NG) && blk < nblk)  // wave-uniform
                 __builtin_amdgcn_global_load_lds(
                         (const void*)(src + blk * 1024),
                         (__attribute__((address_space(3))) void*)(dst + blk * 1024), 16, 0,
@@ -440,8 +446,15 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_ivf_bf2_stream(
             wait_vmcnt<G3>();
         }
     };
-    issue(0, 0);
-    if (NB == 3 && ntile > 1) issue(1, 1);
+    // The sequential form does not stream the padding rows that align a
+    // list to whole tiles (c2: 1 row in 6): of the last tile only the 1 KB
+    // blocks that hold real rows are copied, and its other rows (stale LDS)
+    // get the empty key in the last tile's own loop body.
+    const int nv_last = len - (ntile > 0 ? ntile - 1 : 0) * BV;  // rows of the last tile
+    const int nb_last =
+            PIPE ? NG : __builtin_amdgcn_readfirstlane(min(NG, (nv_last * SR + 1023) >> 10));
+    issue(0, 0, ntile <= 1 ? nb_last : NG);
+    if (NB == 3 && ntile > 1) issue(1, 1, ntile == 2 ? nb_last : NG);
     // epilogue operands, loaded now (their latency hides under the loop)
     const float rmax_l = rmax[l], ynmax_l = ynmax[l];
     const float cnorm_l = PQ ? pcnorm[l] : 0.f;
@@ -523,7 +536,7 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_ivf_bf2_stream(
         float n1[16];
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();  // tile 0 (every wave's part)
-        if (ntile > 1) issue(1, 1);
+        if (ntile > 1) issue(1, 1, NG);
         if (active) {
             acc0 = bf2_block<NS>(tiles + li * SR + 16 * lh, bh, bl);
         }
@@ -540,7 +553,7 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_ivf_bf2_stream(
                 wait_vmcnt<0>();  // tile j + 1 (this wave's part)
                 wait_lgkmcnt0();  // this wave's reads of tile j
                 __builtin_amdgcn_s_barrier();  // tile j + 1 landed, tile j consumed
-                if (j + 2 < ntile) issue(j + 2, b);
+                if (j + 2 < ntile) issue(j + 2, b, NG);
                 const uint8_t* T1 = tiles + (b ^ 1) * TB;
                 if (active) {
                     acc0 = mfma_push(T1, 0, acc1, n1, nullptr, ordbase, tq[1]);
@@ -552,20 +565,28 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_ivf_bf2_stream(
             b ^= 1;
         }
     } else {
-        int b = 0;  // buffer of tile j
-        for (int j = 0; j < ntile; j++) {
+        // tile j in buffer b.  TAIL (the last tile, in its own body so that
+        // the hot loop carries no test): rows from nv_last on are padding or
+        // were not copied; their keys are the empty key
+        auto tile = [&](int j, int b, auto tail_c) {
+            constexpr bool TAIL = decltype(tail_c)::value;
             // tile j landed (this wave's part); with NB = 3 tile j + 1 may still
             // be in flight
             wait_tiles(j + 1 < ntile ? 1 : 0);
             __builtin_amdgcn_s_barrier();  // every wave's part; tile j - 1 consumed
-            if (j + NB - 1 < ntile) issue(j + NB - 1, b == 0 ? NB - 1 : b - 1);  // tile j - 1's buffer
-
+            if (!TAIL && j + NB - 1 < ntile)  // into tile j - 1's buffer
+                issue(j + NB - 1, b == 0 ? NB - 1 : b - 1, j + NB == ntile ? nb_last : NG);
 
             if (active) {
                 const uint32_t ordbase = (uint32_t)j << 4;
                 const uint8_t* T = tiles + b * TB;
+                // TAIL: this lane's row 4 lh + o of the tile is real iff o < vrem
+                const int vrem = nv_last - 4 * lh;
+                const int nb_rows = __builtin_amdgcn_readfirstlane(nv_last);
 #pragma unroll
                 for (int bi = 0; bi < 2; bi++) {
+                    // a block of nothing but such rows would push 16 empty keys
+                    if (TAIL && 32 * bi >= nb_rows) continue;  // wave-uniform
                     const uint8_t* arow = T + (32 * bi + li) * SR + 16 * lh;
                     bf16x8 ah[NS];
 #pragma unroll
@@ -584,8 +605,11 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_ivf_bf2_stream(
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ab, bq, acc, 0, 0, 0);
                         mfma_read_guard();  // key_insert reads acc (inline asm)
 #pragma unroll
-                        for (int r = 0; r < 16; r++)
-                            tq[bi].push(key_insert(fold_key_bits(acc[r]), lowmask, ordbase | (uint32_t)r));
+                        for (int r = 0; r < 16; r++) {
+                            uint32_t key = key_insert(fold_key_bits(acc[r]), lowmask, ordbase | (uint32_t)r);
+                            if (TAIL && 32 * bi + 8 * (r >> 2) + (r & 3) >= vrem) key = 0xffffffffu;
+                            tq[bi].push(key);
+                        }
                         __builtin_amdgcn_sched_barrier(0);
                         continue;
                     }
@@ -598,14 +622,21 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_ivf_bf2_stream(
                         // IP: bias 0 for real rows, +inf for padding
                         const float yv = L2 ? yv0 : (yv0 < WS_INF ? 0.f : WS_INF);
                         const float a = L2 ? fmaf(-2.f, acc[r], xn + yv) : yv - acc[r];
-                        tq[bi].push(key_insert(key_bits<L2>(a), lowmask, ordbase | (uint32_t)r));
+                        uint32_t key = key_insert(key_bits<L2>(a), lowmask, ordbase | (uint32_t)r);
+                        if (TAIL && 32 * bi + 8 * g + c >= vrem) key = 0xffffffffu;
+                        tq[bi].push(key);
                     }
                     // keep the two blocks' live ranges apart (register pressure)
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
+        };
+        int b = 0;  // buffer of tile j
+        for (int j = 0; j + 1 < ntile; j++) {
+            tile(j, b, std::false_type{});
             b = b == NB - 1 ? 0 : b + 1;
         }
+        if (ntile > 0) tile(ntile - 1, b, std::true_type{});
     }
 
     const unsigned long long ft2 = ftrace ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -662,6 +693,13 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_ivf_bf2_stream(
             pr.pad = PQ ? (uint32_t)l : 0u;  // the PQ re-rank's list
             recs[e] = pr;
         }
+    }
+    if (ftrace && lane == 0) {
+        // word 7, byte w: this wave's SIMD_ID (HW_ID bits 5:4) | active << 2 |
+        // row-block mode << 3 (0: both blocks of every tile) | query slice << 5
+        const uint32_t simd = (__builtin_amdgcn_s_getreg(4 | (31 << 11)) >> 4) & 3u;
+        ((uint8_t*)(ftrace + 8 * item + 7))[w] =
+                (uint8_t)(simd | (active ? 4u : 0u) | ((uint32_t)w << 5));
     }
     if (ftrace && t == 0) {  // per-item timestamps (FAISS_AMD_FILTER_TRACE)
         ftrace[8 * item + 0] = ft0;

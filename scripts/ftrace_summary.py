@@ -1,7 +1,10 @@
 """Summarise a per-work-item filter trace (FAISS_AMD_FILTER_TRACE=<file>).
 
 Record per item (8 x u64): t_start, t_loop (query fragments loaded), t_loop_end,
-t_end (s_memrealtime, 100 MHz), HW_ID | XCC_ID << 32, list, len | nQ << 32.
+t_end (s_memrealtime, 100 MHz), HW_ID | XCC_ID << 32, list, len | nQ << 32,
+and one byte per wave w (byte w of word 7): SIMD_ID | active << 2 | row-block
+mode << 3 (0: both blocks of a tile, the kernel's only form; 1 / 2 were block
+0 / 1 of a narrow item in the round-8 split experiment) | query slice << 5.
 """
 import sys
 
@@ -57,6 +60,37 @@ def main(fname):
         m = xcc == x
         if m.any():
             print(f"  xcc {x}: items {m.sum()} rows {ln[m].sum()} end {t3[m].max() * TICK_US:.1f} us")
+    # word 7: one byte per wave (placement and role)
+    wb = np.stack([(a[:, 7] >> np.uint64(8 * w)) & np.uint64(0xff) for w in range(4)],
+                  axis=1).astype(np.int64)
+    simd, act, mode = wb & 3, (wb >> 2) & 1, (wb >> 3) & 3
+    print("  wave -> SIMD, share of items (rows: wave 0..3, columns: SIMD 0..3)")
+    for w in range(4):
+        sh_w = np.bincount(simd[:, w], minlength=4) / len(a)
+        print(f"    wave {w}: " + " ".join(f"{v:5.3f}" for v in sh_w))
+    same = np.all(simd == simd[:, :1], axis=1).sum()
+    distinct = (np.sort(simd, axis=1) == np.arange(4)).all(axis=1).sum()
+    print(f"  items with 4 distinct SIMDs {distinct}  with one SIMD {same}")
+    tot = np.array([act[simd == s_].sum() for s_ in range(4)])
+    blk = np.array([(act * np.where(mode == 0, 2, 1))[simd == s_].sum() for s_ in range(4)])
+    print("  active waves per SIMD: " + " ".join(str(v) for v in tot) +
+          f"  (max / mean {tot.max() / max(tot.mean(), 1):.3f})")
+    print("  active row blocks per SIMD (a wave of a narrow item runs one of two): " +
+          " ".join(str(v) for v in blk) + f"  (max / mean {blk.max() / max(blk.mean(), 1):.3f})")
+    # the same weighted by tiles (MFMA work)
+    wt = np.array([(act * np.where(mode == 0, 2, 1) * ntile[:, None])[simd == s_].sum()
+                   for s_ in range(4)])
+    print("  active row blocks x tiles per SIMD: " + " ".join(str(v) for v in wt) +
+          f"  (max / mean {wt.max() / max(wt.mean(), 1):.3f})")
+    print(f"  narrow-form items (one row block per wave) {(mode.max(axis=1) > 0).sum()}")
+    lo = 0
+    for hi in (32, 64, 96, 128):
+        m = (nq > lo) & (nq <= hi) & (ntile > 0)
+        if m.any():
+            print(f"  nQ {lo + 1:3d}..{hi:3d}: items {m.sum():5d}  loop per tile mean "
+                  f"{per_tile[m].mean():.3f} us  p50 {np.median(per_tile[m]):.3f}  "
+                  f"tiles/item {ntile[m].mean():.2f}")
+        lo = hi
 
 
 if __name__ == "__main__":
