@@ -514,17 +514,119 @@ void query_prep(const float* x, int64_t n, int ldx, int d, float* ref_norms, voi
 
 constexpr int CR_CAP = 512;
 
+// the distance from <x, c>: fma(-2, ip, |x|^2 + |c|^2) clamped at 0 (L2), ip (IP)
+template <bool L2>
+__device__ __forceinline__ float coarse_fold(float ip, float xn, float cn) {
+    if (!L2) return ip;
+    const float dis = fmaf(-2.f, ip, xn + cn);
+    return dis < 0.f ? 0.f : dis;
+}
 // exact coarse distance of centroid j (the fixed BLAS-form order: sequential
-// fma chain for <x, c>, then fma(-2, ip, |x|^2 + |c|^2) clamped at 0 for L2),
-// query from LDS, centroid rows L2-resident (one lane per centroid)
+// fma chain for <x, c>, then coarse_fold), query from LDS, centroid rows
+// L2-resident (one lane per centroid)
 template <bool L2>
 __device__ __forceinline__ float coarse_exact(const float* xs, const float* __restrict__ cent,
                                               int ldc, const float* __restrict__ cnorm, float xn,
                                               int d, int j) {
     const float ip = ip_seq(xs, cent + (int64_t)j * ldc, d);
-    if (!L2) return ip;
-    const float dis = fmaf(-2.f, ip, xn + cnorm[j]);
-    return dis < 0.f ? 0.f : dis;
+    return coarse_fold<L2>(ip, xn, L2 ? cnorm[j] : 0.f);
+}
+
+// Relayed chain: RL lanes share one candidate row, interleaved by float4
+// chunk (chunk c of the row belongs to lane c % RL of the group, as its slot
+// c / RL), so one load instruction reads RL * 16 adjacent bytes per row and a
+// lane has all its slots in flight at once.  The chain then runs one chunk per
+// stage: in stage c every lane takes the accumulator of the lane before it
+// (DPP quad rotation) and adds its slot c / RL to it, times the same slot of
+// the query (held in registers in the rows' layout); the lane whose turn it is
+// (c % RL) thereby continues the live accumulator, which starts as 0.f and
+// sees exactly the fmaf sequence of ip_seq, j ascending: the same bits.  The
+// other lanes' sums in a stage are not used.  (One-wave-per-query loads of
+// one row per lane touch 64 cache lines per instruction for 16 bytes each;
+// this layout touches 16, which is where the time went.)
+// Compiled for d = 4 * RL * CPL with CPL slots per lane, CPL = 4, 6, 8 (d =
+// 64, 96, 128); a guarded form for every other d was measured slower than one
+// lane per row, so those d keep coarse_exact.
+constexpr int RL = 4;           // lanes per row (a DPP quad)
+constexpr int RROWS = 64 / RL;  // rows per pass
+
+template <int CPL>
+__device__ __forceinline__ void relay_fetch(float4 (&r)[CPL], const float* __restrict__ row,
+                                            int l) {
+#pragma unroll
+    for (int u = 0; u < CPL; u++) r[u] = *(const float4*)(row + 4 * (RL * u + l));
+}
+
+// one pass: <x, row> of the group's row (xo: this lane's slots of the query),
+// valid in the group's last lane
+template <int CPL>
+__device__ __forceinline__ float relay_pass(const float4 (&r)[CPL], const float4 (&xo)[CPL]) {
+    float acc = 0.f;
+#pragma unroll
+    for (int u = 0; u < CPL; u++) {
+#pragma unroll
+        for (int s = 0; s < RL; s++) {  // stage RL * u + s
+            // 0x93: quad_perm [3, 0, 1, 2], lane l reads lane (l - 1) % 4
+            acc = __int_as_float(
+                    __builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x93, 0xf, 0xf, false));
+            acc = fmaf(xo[u].x, r[u].x, acc);
+            acc = fmaf(xo[u].y, r[u].y, acc);
+            acc = fmaf(xo[u].z, r[u].z, acc);
+            acc = fmaf(xo[u].w, r[u].w, acc);
+        }
+    }
+    return acc;
+}
+
+// exact coarse distance (coarse_fold of the relayed <x, c_j>, folded by the
+// lane that holds it) of the candidates 64 b + lane < ns (surv[], b < NB,
+// ns >= 1) into dis[b]: passes of RROWS rows, NBUF passes' rows in flight (a
+// pass's buffer is refilled as soon as its chain has run).  Rows past ns
+// repeat the last one.
+template <bool L2, int CPL, int NB>
+__device__ __forceinline__ void relay_dis(const uint32_t* surv, int ns, const float* xsh, float xn,
+                                          const float* __restrict__ cent, int ldc,
+                                          const float* __restrict__ cnorm, int lane,
+                                          float (&dis)[NB], bool trace, unsigned long long& t_f) {
+    const int l = lane & (RL - 1), g = lane / RL;
+    const int P = (ns + RROWS - 1) / RROWS;
+    // the query's slots and NBUF row buffers within 96 VGPRs
+    constexpr int NBUF = CPL > 6 ? 2 : 3;
+    float4 r[NBUF][CPL], xo[CPL];
+#pragma unroll
+    for (int u = 0; u < CPL; u++) xo[u] = *(const float4*)(xsh + 4 * (RL * u + l));
+    float cn[NBUF];
+    auto fetch = [&](float4(&rb)[CPL], float& cnb, int p) {
+        const uint32_t j = surv[min(RROWS * p + g, ns - 1)];
+        relay_fetch<CPL>(rb, cent + (int64_t)j * ldc, l);
+        cnb = L2 ? cnorm[j] : 0.f;
+    };
+    auto pass = [&](const float4(&rb)[CPL], float cnb, int p) {
+        const float acc = coarse_fold<L2>(relay_pass<CPL>(rb, xo), xn, cnb);
+        // candidate RROWS * p + g sits in lane RL * g + RL - 1; its home is
+        // lane (RROWS * p + g) % 64 of batch p / RL
+        const float v = __shfl(acc, RL * (lane & (RROWS - 1)) + RL - 1);
+#pragma unroll
+        for (int b = 0; b < NB; b++)
+            if (b == p / RL && lane / RROWS == (p & (RL - 1))) dis[b] = v;
+    };
+#pragma unroll
+    for (int b = 0; b < NBUF; b++)
+        if (b < P) fetch(r[b], cn[b], b);
+    if (trace) {
+        __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the stamp splits fetch from chain
+        t_f = __builtin_amdgcn_s_memrealtime();
+    }
+#pragma unroll 1
+    for (int p = 0; p < P; p += NBUF) {
+#pragma unroll
+        for (int b = 0; b < NBUF; b++) {
+            if (p + b < P) {
+                pass(r[b], cn[b], p + b);
+                if (p + b + NBUF < P) fetch(r[b], cn[b], p + b + NBUF);
+            }
+        }
+    }
 }
 
 template <bool L2>
@@ -704,16 +806,36 @@ __global__ __launch_bounds__(64, CR_WAVES) void k_coarse_rerank(
     st.overflow = ns > CR_CAP;
     st.fold = fold;
     st.fmask = fmask;
-    bool done = false;
-    unsigned long long t_e = 0ull;
+    bool done = false, relayed = false;
+    unsigned long long t_e = 0ull, t_f = 0ull;
     auto small = [&](auto nbc) {
         constexpr int NB = decltype(nbc)::value;
-        float k1[NB];
+        float k1[NB], dis[NB];
         long long k2[NB];
+        // four lanes per row at d = 64 / 96 / 128 (slots per lane = d / 16),
+        // one lane per row at any other d
+        relayed = ns > 0 && (d == 128 || d == 96 || d == 64);
+#pragma unroll
+        for (int b = 0; b < NB; b++) dis[b] = 0.f;
+        auto relay = [&](auto cplc) {
+            relay_dis<L2, decltype(cplc)::value, NB>(surv, ns, xsh, xn, cent, ldc, cnorm, lane,
+                                                     dis, trace != nullptr, t_f);
+        };
+        if (!relayed) {
+#pragma unroll
+            for (int b = 0; b < NB; b++)
+                if (64 * b + lane < ns)
+                    dis[b] = coarse_exact<L2>(xsh, cent, ldc, cnorm, xn, d, (int)surv[64 * b + lane]);
+        } else if (d == 128) relay(std::integral_constant<int, 8>());
+        else if (d == 96) relay(std::integral_constant<int, 6>());
+        else relay(std::integral_constant<int, 4>());
 #pragma unroll
         for (int b = 0; b < NB; b++) {
             const bool ok = 64 * b + lane < ns;
-            st.emit(ok, ok ? (int)surv[64 * b + lane] : 0, k1[b], k2[b]);
+            k1[b] = WS_INF;
+            k2[b] = WS_NOID;
+            if (ok)
+                to_key(L2 ? 1 : 0, dis[b], (int)surv[64 * b + lane], k1[b], k2[b]);
             if (!(ok && key_admissible(k1[b]))) {
                 k1[b] = WS_INF;
                 k2[b] = WS_NOID;
@@ -760,12 +882,14 @@ __global__ __launch_bounds__(64, CR_WAVES) void k_coarse_rerank(
         trace[8 * q + 3] = t_u;
         trace[8 * q + 4] = t_c;
         trace[8 * q + 5] = t_e;
+        trace[8 * q + 7] = t_f;  // the first passes' rows have arrived (relayed queries)
     }
     if (stats && valid && lane == 0) {
         atomicAdd(&stats[0], (uint32_t)min(ns, CR_CAP));
         atomicAdd(&stats[1], (uint32_t)__popcll(fmask));
         atomicAdd(&stats[2], st.overflow ? 1u : 0u);
         atomicAdd(&stats[3], done ? 0u : 1u);
+        atomicAdd(&stats[4], relayed ? 1u : 0u);
     }
 }
 
@@ -862,8 +986,8 @@ void coarse_bf3_knn(const CoarsePlan& p, const float* x, int64_t n, int ldx, con
     FAISS_THROW_IF_NOT(p.ok);
     static uint32_t* stats = nullptr;  // FAISS_AMD_IVF_STATS debug counters
     const bool dbg = getenv("FAISS_AMD_IVF_STATS") != nullptr;
-    if (dbg && !stats) HIP_CHECK(hipMalloc(&stats, 16));
-    if (dbg) HIP_CHECK(hipMemsetAsync(stats, 0, 16, s));
+    if (dbg && !stats) HIP_CHECK(hipMalloc(&stats, 32));
+    if (dbg) HIP_CHECK(hipMemsetAsync(stats, 0, 32, s));
     FAISS_THROW_IF_NOT(ldx % 4 == 0 && ldc % 4 == 0);
     const int NS = bf3_db(d) / 16;
     // bf16x3 by default.  FAISS_AMD_COARSE_PREC=bf16x2 (two MFMA passes, half
@@ -998,12 +1122,12 @@ void coarse_bf3_knn(const CoarsePlan& p, const float* x, int64_t n, int ldx, con
         }
     }
     if (dbg) {
-        uint32_t h[4];
-        HIP_CHECK(hipMemcpyAsync(h, stats, 16, hipMemcpyDeviceToHost, s));
+        uint32_t h[5];
+        HIP_CHECK(hipMemcpyAsync(h, stats, 20, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         fprintf(stderr, "[faiss_amd] coarse bf3: nq=%lld k=%d survivors/q=%.2f failing streams/q=%.4f "
-                "overflow=%u general-resolve=%u\n", (long long)n, k, h[0] / (double)n,
-                h[1] / (double)n, h[2], h[3]);
+                "overflow=%u general-resolve=%u relayed=%u\n", (long long)n, k, h[0] / (double)n,
+                h[1] / (double)n, h[2], h[3], h[4]);
     }
     HIP_LAUNCH_CHECK();
 }

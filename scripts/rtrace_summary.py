@@ -1,7 +1,11 @@
 """Summarise a re-rank trace (FAISS_AMD_RERANK_TRACE=<file>): per query
 s_memrealtime (100 MHz) stamps: start, end, ns | fails << 32, after U, after
 the candidate list, after the exact evaluation, after round A of a two-round
-query (0: single sweep), rows evaluated exactly."""
+query (0: single sweep), rows evaluated exactly.
+
+A coarse re-rank trace (FAISS_AMD_CRERANK_TRACE=<file>) has the same layout;
+its last word is the stamp taken when the first passes' candidate rows have
+arrived, which splits the exact evaluation into fetch and chain."""
 import sys
 
 import numpy as np
@@ -20,8 +24,14 @@ if two.any():
     ph["  round A (two-round queries)"] = np.where(two, a[:, 6] - a[:, 4], 0)
     ph["  T + round B"] = np.where(two, a[:, 5] - a[:, 6], 0)
     print(f"two-round queries {two.sum()}; exact rows mean {a[:, 7].mean():.1f}")
+fetch = (a[:, 6] == 0) & (a[:, 7] >= a[:, 4]) & (a[:, 7] <= a[:, 5]) & (a[:, 5] > 0)
+if fetch.any():
+    ph["  fetch (rows arrived)"] = np.where(fetch, a[:, 7] - a[:, 4], 0)
+    ph["  chain + fold"] = np.where(fetch, a[:, 5] - a[:, 7], 0)
+    print(f"relayed queries {fetch.sum()}")
 for k, v in ph.items():
-    v = v[(a[:, 5] > 0) & (two if k.startswith("  ") else True)] * us
+    sub = fetch if k in ("  fetch (rows arrived)", "  chain + fold") else two
+    v = v[(a[:, 5] > 0) & (sub if k.startswith("  ") else True)] * us
     print(f"  {k:28s} mean {v.mean():6.2f} p50 {np.median(v):6.2f} p95 {np.percentile(v, 95):6.2f} us")
 end = np.sort(a[:, 1] - a[:, 0].min()) * us
 print("  in flight (mean over span):", f"{((a[:, 1] - a[:, 0]).sum() * us) / (end[-1]):.0f}")
