@@ -247,6 +247,15 @@ def _declare(L):
         "faiss_Index_reconstruct_n": (C.c_int, [_P, _I64, _I64, _P]),
         "faiss_Index_assign": (C.c_int, [_P, _I64, _P, _P, _I64]),
         "faiss_IndexIVF_imbalance_factor": (C.c_double, [_P]),
+        "faiss_IndexRefineFlat_new": (C.c_int, [C.POINTER(_P), _P]),
+        "faiss_IndexRefineFlat_own_fields": (C.c_int, [_P]),
+        "faiss_IndexRefineFlat_set_own_fields": (None, [_P, C.c_int]),
+        "faiss_IndexRefineFlat_k_factor": (C.c_float, [_P]),
+        "faiss_IndexRefineFlat_set_k_factor": (None, [_P, C.c_float]),
+        "faiss_amd_IndexRefine_base_index": (_P, [_P]),
+        "faiss_amd_IndexRefine_refine_index": (_P, [_P]),
+        "faiss_amd_IndexRefineSearchParameters_new": (C.c_int, [C.c_float, _P, C.POINTER(_P)]),
+        "faiss_amd_IndexRefineSearchParameters_free": (None, [_P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -735,6 +744,39 @@ class IndexIVFScalarQuantizer(IndexIVF):
             self.h, x.shape[0], _ptr(x), _ptr(ids) if ids is not None else None, _ptr(pre)))
 
 
+class IndexRefineFlat(Index):
+    """faiss.IndexRefineFlat: searches k * k_factor candidates in base_index and
+    re-ranks them with exact distances from a flat copy of the vectors."""
+
+    def __init__(self, base_index=None, handle=None, owner=None):
+        if handle is None:
+            p = C.c_void_p()
+            _check(lib().faiss_IndexRefineFlat_new(C.byref(p), base_index.h))
+            handle = p
+            self._base = base_index  # must outlive the wrapper (own_fields = false)
+        super().__init__(handle, owner)
+
+    @property
+    def k_factor(self):
+        return lib().faiss_IndexRefineFlat_k_factor(self.h)
+
+    @k_factor.setter
+    def k_factor(self, v):
+        lib().faiss_IndexRefineFlat_set_k_factor(self.h, float(v))
+
+    @property
+    def own_fields(self):
+        return bool(lib().faiss_IndexRefineFlat_own_fields(self.h))
+
+    @property
+    def base_index(self):
+        return _wrap(lib().faiss_amd_IndexRefine_base_index(self.h), owner=self)
+
+    @property
+    def refine_index(self):
+        return _wrap(lib().faiss_amd_IndexRefine_refine_index(self.h), owner=self)
+
+
 class IndexShardsIVF(IndexIVF):
     """faiss/IndexShardsIVF.h: shards sharing one coarse quantizer; shards on
     other devices than the quantizer are searched over RCCL (shards.cpp)."""
@@ -848,6 +890,24 @@ class SearchParametersIVF:
             pass
 
 
+class IndexRefineSearchParameters:
+    """faiss.IndexRefineSearchParameters: the call's k_factor and the
+    parameters handed to the base index (e.g. a SearchParametersIVF)."""
+
+    def __init__(self, k_factor=1.0, base_index_params=None):
+        p = C.c_void_p()
+        _check(lib().faiss_amd_IndexRefineSearchParameters_new(
+            float(k_factor), base_index_params.h if base_index_params else None, C.byref(p)))
+        self.h = p
+        self._base = base_index_params  # must outlive the searches that use it
+
+    def __del__(self):
+        try:
+            lib().faiss_amd_IndexRefineSearchParameters_free(self.h)
+        except Exception:
+            pass
+
+
 class ParameterSpace:
     def __init__(self):
         p = C.c_void_p()
@@ -896,7 +956,8 @@ def _wrap(h, owner=None):
         return IndexShardsIVF.__new__(IndexShardsIVF)._init_from(h, owner)
     cls = {"IndexIVFPQ": IndexIVFPQ, "IndexIVFFlat": IndexIVFFlat,
            "IndexIVFScalarQuantizer": IndexIVFScalarQuantizer,
-           "IndexHNSWFlat": IndexHNSWFlat, "IndexFlat": IndexFlat}.get(t)
+           "IndexHNSWFlat": IndexHNSWFlat, "IndexFlat": IndexFlat,
+           "IndexRefineFlat": IndexRefineFlat}.get(t)
     if cls is None:
         return Index(h, owner)
     return cls(handle=h, owner=owner)

@@ -28,6 +28,9 @@ struct SearchParamsC {
     bool has_q = false;
     SearchParamsC() { ivf.nprobe = 1; }
 };
+struct RefineParamsC {
+    IndexRefineSearchParameters refine;
+};
 
 inline Index* IX(FaissIndex* p) { return reinterpret_cast<Index*>(p); }
 inline const Index* IX(const FaissIndex* p) { return reinterpret_cast<const Index*>(p); }
@@ -94,8 +97,12 @@ int faiss_Index_search(const FaissIndex* index, idx_t n, const float* x, idx_t k
     C_CATCH
 }
 
+// every FaissSearchParameters* points at an object whose first member is the
+// C++ parameter object: SearchParamsC (ivf) or RefineParamsC (refine)
 static const SearchParameters* resolve_params(const FaissSearchParameters* p) {
     if (!p) return nullptr;
+    auto base = reinterpret_cast<const SearchParameters*>(p);
+    if (dynamic_cast<const IndexRefineSearchParameters*>(base)) return base;
     auto sp = reinterpret_cast<const SearchParamsC*>(p);
     return &sp->ivf;
 }
@@ -297,18 +304,58 @@ void faiss_IndexFlat_xb(FaissIndexFlat* index, float** p_xb, size_t* p_size) {
     *p_size = f->xb.size();
 }
 
+// ---------------- IndexRefineFlat (c_api/IndexFlat_c.h:89-107, IndexFlat_c.cpp:113-132)
+int faiss_IndexRefineFlat_new(FaissIndexRefineFlat** p_index, FaissIndex* base_index) {
+    C_TRY* p_index = FX(new IndexRefineFlat(IX(base_index)));
+    C_CATCH
+}
+void faiss_IndexRefineFlat_free(FaissIndexRefineFlat* obj) { delete IX(obj); }
+FaissIndexRefineFlat* faiss_IndexRefineFlat_cast(FaissIndex* index) {
+    return dynamic_cast<IndexRefineFlat*>(IX(index)) ? index : nullptr;
+}
+// (getters never throw: 0 / no-op on a wrong type)
+static IndexRefine* RFm(const FaissIndex* i) {
+    return dynamic_cast<IndexRefine*>(const_cast<Index*>(IX(i)));
+}
+int faiss_IndexRefineFlat_own_fields(const FaissIndexRefineFlat* i) {
+    auto r = RFm(i);
+    return r && r->own_fields ? 1 : 0;
+}
+void faiss_IndexRefineFlat_set_own_fields(FaissIndexRefineFlat* i, int v) {
+    if (auto r = RFm(i)) r->own_fields = v != 0;
+}
+float faiss_IndexRefineFlat_k_factor(const FaissIndexRefineFlat* i) {
+    auto r = RFm(i);
+    return r ? r->k_factor : 0.f;
+}
+void faiss_IndexRefineFlat_set_k_factor(FaissIndexRefineFlat* i, float v) {
+    if (auto r = RFm(i)) r->k_factor = v;
+}
+FaissIndex* faiss_amd_IndexRefine_base_index(const FaissIndex* i) {
+    auto r = RFm(i);
+    return r ? FX(r->base_index) : nullptr;
+}
+FaissIndex* faiss_amd_IndexRefine_refine_index(const FaissIndex* i) {
+    auto r = RFm(i);
+    return r ? FX(r->refine_index) : nullptr;
+}
+int faiss_amd_IndexRefineSearchParameters_new(float k_factor, FaissSearchParameters* base_params,
+                                              FaissSearchParameters** p_sp) {
+    C_TRY auto sp = new RefineParamsC();
+    sp->refine.k_factor = k_factor;
+    sp->refine.base_index_params = const_cast<SearchParameters*>(resolve_params(base_params));
+    *p_sp = reinterpret_cast<FaissSearchParameters*>(sp);
+    C_CATCH
+}
+void faiss_amd_IndexRefineSearchParameters_free(FaissSearchParameters* obj) {
+    delete reinterpret_cast<RefineParamsC*>(obj);
+}
+
 // ---------------- IndexIVF (getters never throw: 0 / no-op on a wrong type)
 static const IndexIVF* IVFc(const FaissIndexIVF* i) { return dynamic_cast<const IndexIVF*>(IX(i)); }
 static IndexIVF* IVFm(FaissIndexIVF* i) { return dynamic_cast<IndexIVF*>(IX(i)); }
 const char* faiss_amd_Index_type(const FaissIndex* i) {
-    const Index* x = IX(i);
-    if (dynamic_cast<const IndexShardsIVF*>(x)) return "IndexShardsIVF";
-    if (dynamic_cast<const IndexIVFPQ*>(x)) return "IndexIVFPQ";
-    if (dynamic_cast<const IndexIVFScalarQuantizer*>(x)) return "IndexIVFScalarQuantizer";
-    if (dynamic_cast<const IndexIVFFlat*>(x)) return "IndexIVFFlat";
-    if (dynamic_cast<const IndexHNSW*>(x)) return "IndexHNSWFlat";
-    if (dynamic_cast<const IndexFlat*>(x)) return "IndexFlat";
-    return "Index";
+    return index_type_name(IX(i));
 }
 size_t faiss_IndexIVF_nlist(const FaissIndexIVF* i) {
     if (auto s = dynamic_cast<const IndexShardsIVF*>(IX(i))) return s->nlist;
@@ -806,6 +853,17 @@ int faiss_ParameterSpace_set_index_parameter(const FaissParameterSpace*, FaissIn
     // faiss/AutoTune.cpp:468-557 subset
     C_TRY std::string n(name);
     Index* ix = IX(index);
+    // faiss/AutoTune.cpp:483-491: k_factor_rf is the wrapper's, every other
+    // name goes to its base index
+    while (auto rf = dynamic_cast<IndexRefine*>(ix)) {
+        if (n == "k_factor_rf") {
+            rf->k_factor = (float)(int)val;
+            return 0;
+        }
+        FAISS_THROW_IF_NOT(rf->base_index);
+        ix = rf->base_index;
+        index = FX(ix);
+    }
     if (n == "nprobe") {
         if (auto s = dynamic_cast<IndexShardsIVF*>(ix)) {
             s->nprobe = (size_t)val;
@@ -952,6 +1010,10 @@ int faiss_amd_last_kernel_times(const FaissIndex* index, int* n_kernels, char* n
                                 double* millis, double* units) {
     C_TRY const Index* ix = IX(index);
     std::vector<KernelTimes*> all{&ix->ktimes};
+    if (auto rf = dynamic_cast<const IndexRefine*>(ix)) {  // then the base index's stages
+        ix = rf->base_index;
+        all.push_back(&ix->ktimes);
+    }
     if (auto ivf = dynamic_cast<const IndexIVF*>(ix)) all.push_back(&ivf->quantizer->ktimes);
     if (auto sh = dynamic_cast<const IndexShardsIVF*>(ix)) {
         all.push_back(&sh->quantizer->ktimes);
@@ -984,6 +1046,10 @@ int faiss_amd_IndexIVF_debug_rows(const FaissIndex* index, int what, int64_t row
 int faiss_amd_reset_kernel_times(FaissIndex* index) {
     C_TRY Index* ix = IX(index);
     ix->ktimes.clear();
+    if (auto rf = dynamic_cast<IndexRefine*>(ix)) {
+        ix = rf->base_index;
+        ix->ktimes.clear();
+    }
     if (auto ivf = dynamic_cast<IndexIVF*>(ix)) ivf->quantizer->ktimes.clear();
     if (auto sh = dynamic_cast<IndexShardsIVF*>(ix)) {
         sh->quantizer->ktimes.clear();

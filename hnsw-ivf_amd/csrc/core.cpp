@@ -165,6 +165,18 @@ void Index::range_search(idx_t, const float*, float, RangeSearchResult*,
 
 hipStream_t Index::stream() const { return device_context(device).stream; }
 
+const char* index_type_name(const Index* x) {
+    if (dynamic_cast<const IndexRefineFlat*>(x)) return "IndexRefineFlat";
+    if (dynamic_cast<const IndexRefine*>(x)) return "IndexRefine";
+    if (dynamic_cast<const IndexShardsIVF*>(x)) return "IndexShardsIVF";
+    if (dynamic_cast<const IndexIVFPQ*>(x)) return "IndexIVFPQ";
+    if (dynamic_cast<const IndexIVFScalarQuantizer*>(x)) return "IndexIVFScalarQuantizer";
+    if (dynamic_cast<const IndexIVFFlat*>(x)) return "IndexIVFFlat";
+    if (dynamic_cast<const IndexHNSW*>(x)) return "IndexHNSWFlat";
+    if (dynamic_cast<const IndexFlat*>(x)) return "IndexFlat";
+    return "Index";
+}
+
 // Host entry: upload (zero-padded rows) into this index's cached device
 // buffers, search_device, download.  (HIP stages pageable host memory through
 // its own pinned buffers; a pinned caller buffer goes straight to the DMA

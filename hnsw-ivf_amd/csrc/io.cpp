@@ -20,6 +20,7 @@
 //             vector<int> levels, vector<size_t> offsets, vector<i32>
 //             neighbors, entry_point:i32, max_level, efConstruction,
 //             efSearch:int, dummy int), storage index         (:300-316,760-778)
+//   IxRF    = header, base index, refine index, k_factor:f32    (:744-752)
 //   vectors carry a size_t element-count prefix (faiss/impl/io_macros.h:62-67)
 //   fourcc = little-endian chars (faiss/impl/io.cpp:237-241)
 #include <fcntl.h>
@@ -497,6 +498,13 @@ void write_index_impl(const Index* idx, Writer& w) {
         w.one<size_t>(sq->code_size);
         w.one<uint8_t>(sq->by_residual ? 1 : 0);
         write_invlists(sq->invlists.get(), w);
+    } else if (auto rf = dynamic_cast<const IndexRefine*>(idx)) {
+        // faiss/impl/index_write.cpp:744-752
+        w.one(fourcc("IxRF"));
+        write_header(rf, w);
+        write_index_impl(rf->base_index, w);
+        write_index_impl(rf->refine_index, w);
+        w.one<float>(rf->k_factor);
     } else {
         FAISS_THROW_MSG("don't know how to serialize this type of index");
     }
@@ -602,6 +610,26 @@ Index* read_index_impl(Reader& r, int io_flags) {
         }
         return ivf;
     }
+    if (h == fourcc("IxRF")) {
+        // faiss/impl/index_read.cpp:913-928: a flat refine index makes the
+        // result an IndexRefineFlat; both own flags are set
+        Header hd = read_header(r);
+        std::unique_ptr<Index> base(read_index_impl(r, io_flags));
+        std::unique_ptr<Index> refine(read_index_impl(r, io_flags));
+        FAISS_THROW_IF_NOT_MSG(base && refine, "IxRF: base or refine index missing");
+        FAISS_THROW_IF_NOT_MSG(dynamic_cast<IndexFlat*>(refine.get()),
+                               std::string("IxRF: a refine index of type ") +
+                                       index_type_name(refine.get()) +
+                                       " is not served (IndexFlat only)");
+        auto rf = std::make_unique<IndexRefineFlat>();
+        apply_header(rf.get(), hd);
+        rf->device = base->device;
+        rf->base_index = base.release();
+        rf->refine_index = refine.release();
+        rf->own_fields = rf->own_refine_index = true;
+        rf->k_factor = r.one<float>();
+        return rf.release();
+    }
     FAISS_THROW_MSG("Index type " + fourcc_str(h) + " not supported on this path");
 }
 }  // namespace
@@ -650,8 +678,36 @@ Index* read_index(const char* fname, int io_flags) {
 
 // ---------------------------------------------------------------- factory
 // faiss/index_factory.cpp:242-345 subset.
+namespace {
+Index* factory_plain(int d, const std::string& s, MetricType metric);
+}
+
 Index* index_factory(int d, const char* description, MetricType metric) {
-    std::string s(description);
+    // faiss/index_factory.cpp:700-716: "<base>,RFlat" / "<base>,Refine(<desc>)"
+    // with k_factor 1.  Only a flat refine index is served, so both spellings
+    // give an IndexRefineFlat (what the reference's reader makes of either).
+    std::string s(description), refine;
+    const size_t pr = s.rfind(",Refine(");
+    if (s.size() > 6 && s.compare(s.size() - 6, 6, ",RFlat") == 0) {
+        refine = "Flat";
+        s.erase(s.size() - 6);
+    } else if (pr != std::string::npos && pr > 0 && s.back() == ')' && s.size() > pr + 9) {
+        refine = s.substr(pr + 8, s.size() - pr - 9);
+        s.erase(pr);
+    }
+    if (refine.empty()) return factory_plain(d, s, metric);
+    FAISS_THROW_IF_NOT_MSG(refine == "Flat", "IndexRefine: a refine index of type " + refine +
+                                                     " is not served (Flat only)");
+    std::unique_ptr<Index> base(factory_plain(d, s, metric));
+    auto rf = std::make_unique<IndexRefineFlat>(base.get());
+    base.release();
+    rf->own_fields = true;
+    return rf.release();
+}
+
+namespace {
+Index* factory_plain(int d, const std::string& s_in, MetricType metric) {
+    std::string s(s_in);
     auto parse_int = [&](size_t& pos) {
         size_t st = pos;
         while (pos < s.size() && isdigit((unsigned char)s[pos])) pos++;
@@ -733,5 +789,6 @@ Index* index_factory(int d, const char* description, MetricType metric) {
     ivf->own_fields = true;
     return ivf;
 }
+}  // namespace
 
 }  // namespace faiss_amd

@@ -288,6 +288,29 @@ void select_rows_exact(const float* D, int64_t nx, int64_t ny, int64_t ldD, int 
                        int64_t col0, float* out_d, OutIdx* out_i, int64_t ldo, hipStream_t s,
                        DeviceBuffer* scratch = nullptr);
 
+// ---------------- IndexRefineFlat (kernels_refine.hip) ----------------
+// keys_out[q][j] = ex_key of the exact reference-order distance (ref_arith.h)
+// between query q and row labels[q][j] of the flat storage xb [ntotal][ldb];
+// EX_SKIP where the label is < 0 or >= ntotal (never dereferenced).
+// ntotal < 2^32.
+void refine_flat_distances(const float* x, int ldx, int64_t n, int d, int l2,
+                           const int64_t* labels, int64_t k_base, const float* xb, int ldb,
+                           int64_t ntotal, uint32_t* keys_out, hipStream_t s);
+// the same evaluator over a range result on the device: query i's hits are
+// labels[lims[i] .. lims[i + 1]); dis_out gets plain floats (+inf L2 / -inf IP
+// for a label outside the storage)
+void refine_range_distances(const float* x, int ldx, int64_t n, int d, int l2,
+                            const unsigned long long* lims, const int64_t* labels,
+                            const float* xb, int ldb, int64_t ntotal, float* dis_out,
+                            hipStream_t s);
+// reorder_2_heaps (faiss/IndexRefine.cpp:65-87) of refine_flat_distances' keys:
+// k_ex_select over [n][k_base] keys / labels in base-result order -> D, I
+// [n][k], pads (FLT_MAX / -FLT_MAX, -1).  D / I may be the base buffers when
+// k_base == k.  k > kMaxKExact runs with global scratch (required then).
+void refine_select(const uint32_t* keys, const int64_t* labels, int64_t n, int64_t k_base, int k,
+                   int metric_l2, float* D, int64_t* I, hipStream_t s,
+                   DeviceBuffer* scratch = nullptr);
+
 // IndexIVFStats counters of a batch (faiss/IndexIVF.cpp:1184-1198):
 // stats[0] += non-empty lists visited, stats[1] += codes scanned (device)
 void ivf_visit_stats(const int32_t* assign, int64_t total, const uint32_t* list_len, int nlist,

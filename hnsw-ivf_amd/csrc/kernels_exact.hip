@@ -274,6 +274,19 @@ struct SrcDense {
     __device__ void done(int64_t) const {}
 };
 
+// IndexRefine's re-ranked candidates (kernels_refine.hip): k_base keys per
+// query in the base result's order (arrival rank = position in the base row,
+// faiss/IndexRefine.cpp:65-87 reorder_2_heaps), labels = the base's labels
+struct SrcRefine {
+    const uint32_t* keys;
+    const int64_t* labels;
+    int64_t k_base;
+    __device__ int64_t count(int64_t) const { return k_base; }
+    __device__ uint32_t key(int64_t q, int64_t i) const { return keys[q * k_base + i]; }
+    __device__ int64_t label(int64_t q, int64_t i) const { return labels[q * k_base + i]; }
+    __device__ void done(int64_t) const {}
+};
+
 // GS: the collection arrays in global scratch (gs_words 64-bit words per
 // query) instead of LDS — k beyond what one work group's LDS holds
 template <class Src, class OutIdx, bool GS = false>
@@ -613,6 +626,34 @@ void select_rows_exact(const float* Dt, int64_t nx, int64_t ny, int64_t ldD, int
         HIP_LAUNCH_CHECK();
     }
 }
+// labels / D and I may alias when k_base == k (ldo == k): a work group reads
+// its query's labels before the barrier that precedes its writes
+void refine_select(const uint32_t* keys, const int64_t* labels, int64_t n, int64_t k_base, int k,
+                   int metric_l2, float* D, int64_t* I, hipStream_t s, DeviceBuffer* scratch) {
+    if (n <= 0) return;
+    FAISS_THROW_IF_NOT_FMT(k >= 1 && k <= k_base, "k = %d must be in [1, k_base = %lld]", k,
+                           (long long)k_base);
+    if (k <= kMaxKExact) {
+        SrcRefine src{keys, labels, k_base};
+        k_ex_select<SrcRefine, int64_t><<<kgrid(n, 256), dim3(256), select_lds(k), s>>>(
+                src, k, metric_l2, D, I, k);
+        HIP_LAUNCH_CHECK();
+        return;
+    }
+    FAISS_THROW_IF_NOT_MSG(scratch, "refine_select: k > 2048 needs a scratch buffer");
+    const int64_t words = (int64_t)cdiv(select_lds(k), sizeof(unsigned long long));
+    const int64_t qc = std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)256 << 20) / (8 * words)));
+    scratch->reserve((size_t)qc * words * 8);
+    for (int64_t q0 = 0; q0 < n; q0 += qc) {
+        const int64_t nq = std::min(qc, n - q0);
+        SrcRefine src{keys + q0 * k_base, labels + q0 * k_base, k_base};
+        k_ex_select<SrcRefine, int64_t, true><<<kgrid(nq, 256), dim3(256), 0, s>>>(
+                src, k, metric_l2, D + q0 * k, I + q0 * k, k, scratch->as<unsigned long long>(),
+                words);
+        HIP_LAUNCH_CHECK();
+    }
+}
+
 template void select_rows_exact<int32_t>(const float*, int64_t, int64_t, int64_t, int, int,
                                          int64_t, float*, int32_t*, int64_t, hipStream_t,
                                          DeviceBuffer*);

@@ -82,6 +82,11 @@ using faiss_amd::ProductQuantizer;
 using faiss_amd::IndexIVFScalarQuantizer;
 using faiss_amd::ScalarQuantizer;
 
+// faiss/IndexRefine.h
+using faiss_amd::IndexRefine;
+using faiss_amd::IndexRefineFlat;
+using faiss_amd::IndexRefineSearchParameters;
+
 // faiss/IndexShardsIVF.h
 using faiss_amd::IndexShardsIVF;
 

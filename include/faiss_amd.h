@@ -3,7 +3,7 @@
 // Mirrors the reference faiss::Index hierarchy for the hot path
 // (faiss/Index.h:108-181, faiss/IndexFlat.h, faiss/IndexIVF.h:39-587,
 // faiss/IndexIVFFlat.h, faiss/IndexIVFPQ.h, faiss/IndexScalarQuantizer.h, faiss/IndexHNSW.h,
-// faiss/IndexShardsIVF.h): same class names, method signatures, argument
+// faiss/IndexShardsIVF.h, faiss/IndexRefine.h): same class names, method signatures, argument
 // meaning and exceptions, in namespace faiss_amd.  Indexes are GPU-resident:
 // host mirrors keep the faiss data structures (for I/O and reconstruction),
 // HBM holds the search layout.  `search()` takes host pointers and is
@@ -257,6 +257,9 @@ struct Index {
     mutable DeviceBuffer h_x_, h_d_, h_i_;
     mutable std::atomic<uint64_t> version_{0};
 };
+
+// class name of an index's dynamic type ("IndexIVFPQ", "IndexRefineFlat", ...)
+const char* index_type_name(const Index* idx);
 
 // ---------------------------------------------------------------- flat
 // faiss/IndexFlat.h: exhaustive search.  Coarse quantizer of the IVF path.
@@ -860,6 +863,68 @@ struct IndexIVFScalarQuantizer : IndexIVF {
     mutable DeviceBuffer d_trained_, d_cent_;
 };
 
+// ---------------------------------------------------------------- refine
+// faiss/IndexRefine.h:17-24
+struct IndexRefineSearchParameters : SearchParameters {
+    float k_factor = 1;
+    SearchParameters* base_index_params = nullptr;  // not owned
+};
+
+// faiss/IndexRefine.h:26-80: search k * k_factor candidates in base_index,
+// replace their distances by refine_index's exact ones, keep the best k.  On
+// this path refine_index is an IndexFlat (IndexRefineFlat); labels are row
+// numbers of that storage (add gives both indexes sequential ids; there is no
+// add_with_ids).
+struct IndexRefine : Index {
+    Index* base_index = nullptr;
+    Index* refine_index = nullptr;
+    bool own_fields = false;        // base_index deleted with this object
+    bool own_refine_index = false;  // refine_index deleted with this object
+    float k_factor = 1;
+
+    IndexRefine(Index* base_index, Index* refine_index);
+    IndexRefine();
+    ~IndexRefine() override;
+
+    void train(idx_t n, const float* x) override;
+    void add(idx_t n, const float* x) override;
+    void reset() override;
+    void reconstruct(idx_t key, float* recons) const override;
+    // faiss/IndexRefine.cpp:274-337: base search of k_base = idx_t(k *
+    // k_factor) candidates, exact distances (kernels_refine.hip), the
+    // reference heap's top k (kernels_exact.hip), all on `stream`
+    void search_device(idx_t n, const float* x, int ldx, idx_t k, float* distances,
+                       idx_t* labels, const SearchParameters* params,
+                       hipStream_t stream) const override;
+    // faiss/IndexRefine.cpp:169-206: the base's hits with exact distances
+    // (not filtered by the radius again)
+    void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result,
+                      const SearchParameters* params = nullptr) const override;
+    void sync_device() const override;
+    void fold_device_stats() const override;
+    uint64_t content_version() const override {
+        return version_.load() + (base_index ? base_index->content_version() : 0) +
+               (refine_index ? refine_index->content_version() : 0);
+    }
+
+   protected:
+    // the refine index as the flat storage this path serves; throws, naming
+    // the type found, when it is anything else
+    const IndexFlat* flat_storage() const;
+    mutable std::recursive_mutex mu_;
+    mutable StreamOrder order_;  // calls on different streams share the scratch
+    mutable DeviceBuffer s_bd_, s_bi_, s_keys_, s_sel_;
+};
+
+// faiss/IndexRefine.h:82-105
+struct IndexRefineFlat : IndexRefine {
+    // an empty base index; owns a new IndexFlat(d, metric); own_fields false
+    explicit IndexRefineFlat(Index* base_index);
+    // a populated base index and its base_index->ntotal vectors
+    IndexRefineFlat(Index* base_index, const float* xb);
+    IndexRefineFlat();
+};
+
 // ---------------------------------------------------------------- shards
 // faiss/IndexShardsIVF.h:19-40 — shards sharing one coarse quantizer.
 struct IndexShardsIVF : Index {
@@ -951,7 +1016,8 @@ Index* read_index(const char* fname, int io_flags = 0);
 void write_index_ondisk(const Index* idx, const char* fname, const char* lists_fname);
 Index* read_index(FILE* f, int io_flags = 0);
 
-// faiss/index_factory.h (subset: Flat, IVFn[_HNSWm],Flat|PQm[xb][np]|SQ8|SQfp16, HNSWm)
+// faiss/index_factory.h (subset: Flat, IVFn[_HNSWm],Flat|PQm[xb][np]|SQ8|SQfp16, HNSWm,
+// each optionally followed by ",RFlat" / ",Refine(Flat)")
 Index* index_factory(int d, const char* description, MetricType metric = METRIC_L2);
 
 // The reference's IndexIVF::search cuts a batch into min(omp threads, n)

@@ -198,6 +198,33 @@ FaissIndexFlat* faiss_IndexFlat_cast(FaissIndex* index);
 FaissIndexFlatIP* faiss_IndexFlatIP_cast(FaissIndex* index);
 FaissIndexFlatL2* faiss_IndexFlatL2_cast(FaissIndex* index);
 
+/* ---------------- IndexRefineFlat (c_api/IndexFlat_c.h:89-107) ----------------
+ * Searches k * k_factor candidates in base_index (a fast, compressed index)
+ * and re-ranks them with exact distances from a flat copy of the vectors. */
+typedef struct FaissIndex_H FaissIndexRefineFlat;
+/* IndexFlat_c.h:96-98: base_index must be empty; it is not owned until
+ * set_own_fields(index, 1) */
+int faiss_IndexRefineFlat_new(FaissIndexRefineFlat** p_index, FaissIndex* base_index);
+void faiss_IndexRefineFlat_free(FaissIndexRefineFlat* obj);          /* :100 */
+FaissIndexRefineFlat* faiss_IndexRefineFlat_cast(FaissIndex* index); /* :101 */
+int faiss_IndexRefineFlat_own_fields(const FaissIndexRefineFlat*);   /* :103 */
+void faiss_IndexRefineFlat_set_own_fields(FaissIndexRefineFlat*, int);
+/* :105-107: factor between the k of a search and the k asked of base_index (>= 1) */
+float faiss_IndexRefineFlat_k_factor(const FaissIndexRefineFlat*);
+void faiss_IndexRefineFlat_set_k_factor(FaissIndexRefineFlat*, float);
+/* not in the reference C API: the wrapper's two indexes (owned by it or by
+ * the caller as own_fields says; NULL when the index is no IndexRefine) */
+FaissIndex* faiss_amd_IndexRefine_base_index(const FaissIndex* index);
+FaissIndex* faiss_amd_IndexRefine_refine_index(const FaissIndex* index);
+/* faiss/IndexRefine.h:17-24 IndexRefineSearchParameters: k_factor of the call
+ * and the parameters handed to base_index (may be NULL; not owned, must
+ * outlive the call) */
+int faiss_amd_IndexRefineSearchParameters_new(
+        float k_factor,
+        FaissSearchParameters* base_index_params,
+        FaissSearchParameters** p_sp);
+void faiss_amd_IndexRefineSearchParameters_free(FaissSearchParameters* obj);
+
 /* ---------------- IndexIVF (c_api/IndexIVF_c.h) ---------------- */
 size_t faiss_IndexIVF_nlist(const FaissIndexIVF*);              /* :59 */
 size_t faiss_IndexIVF_nprobe(const FaissIndexIVF*);             /* :61 */
