@@ -147,6 +147,10 @@ def _declare(L):
         "faiss_SearchParametersIVF_nprobe": (C.c_size_t, [_P]),
         "faiss_SearchParametersIVF_set_nprobe": (None, [_P, C.c_size_t]),
         "faiss_amd_SearchParametersIVF_set_quantizer_efSearch": (None, [_P, C.c_int]),
+        "faiss_amd_SearchParametersIVF_set_quantizer_hnsw": (None, [_P, C.c_int, C.c_int, C.c_int]),
+        "faiss_amd_SearchParametersIVF_set_quantizer_params": (None, [_P, _P]),
+        "faiss_amd_SearchParametersHNSW_new": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P]),
+        "faiss_amd_SearchParametersHNSW_free": (None, [_P]),
         "faiss_IndexFlat_new_with": (C.c_int, [C.POINTER(_P), _I64, C.c_int]),
         "faiss_IndexFlatL2_new_with": (C.c_int, [C.POINTER(_P), _I64]),
         "faiss_IndexFlatIP_new_with": (C.c_int, [C.POINTER(_P), _I64]),
@@ -204,6 +208,10 @@ def _declare(L):
         "faiss_amd_IndexHNSWFlat_new_with": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int]),
         "faiss_amd_IndexHNSW_efSearch": (C.c_int, [_P]),
         "faiss_amd_IndexHNSW_set_efSearch": (None, [_P, C.c_int]),
+        "faiss_amd_IndexHNSW_check_relative_distance": (C.c_int, [_P]),
+        "faiss_amd_IndexHNSW_set_check_relative_distance": (None, [_P, C.c_int]),
+        "faiss_amd_IndexHNSW_search_bounded_queue": (C.c_int, [_P]),
+        "faiss_amd_IndexHNSW_set_search_bounded_queue": (None, [_P, C.c_int]),
         "faiss_amd_IndexHNSW_efConstruction": (C.c_int, [_P]),
         "faiss_amd_IndexHNSW_set_efConstruction": (None, [_P, C.c_int]),
         "faiss_amd_IndexHNSW_storage": (_P, [_P]),
@@ -229,6 +237,7 @@ def _declare(L):
         "faiss_amd_set_device": (C.c_int, [C.c_int]),
         "faiss_amd_Index_sync_device": (C.c_int, [_P]),
         "faiss_amd_Index_search_device": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+        "faiss_amd_Index_search_device_with_params": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P]),
         "faiss_amd_IndexIVF_search_preassigned_device": (C.c_int, [_P, _I64, _P, _I64, C.c_int, _P, _P, _P, _P, _P]),
         "faiss_amd_IndexIVF_quantize_device": (C.c_int, [_P, _I64, _P, C.c_int, _P, _P, _P]),
         "faiss_amd_merge_knn_results_device": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
@@ -378,7 +387,12 @@ class Index:
     def sync_device(self):
         _check(lib().faiss_amd_Index_sync_device(self.h))
 
-    def search_device(self, n, x_ptr, k, D_ptr, I_ptr, stream=None):
+    def search_device(self, n, x_ptr, k, D_ptr, I_ptr, stream=None, params=None):
+        if params is not None:
+            _check(lib().faiss_amd_Index_search_device_with_params(
+                self.h, n, C.c_void_p(x_ptr), k, params.h, C.c_void_p(D_ptr), C.c_void_p(I_ptr),
+                C.c_void_p(stream or 0)))
+            return
         _check(lib().faiss_amd_Index_search_device(self.h, n, C.c_void_p(x_ptr), k,
                                                    C.c_void_p(D_ptr), C.c_void_p(I_ptr),
                                                    C.c_void_p(stream or 0)))
@@ -443,6 +457,26 @@ class IndexHNSW(Index):
         lib().faiss_amd_IndexHNSW_set_efSearch(self.h, int(v))
 
     @property
+    def check_relative_distance(self):
+        """hnsw.check_relative_distance: False stops level 0 after efSearch
+        hops instead of by the relative-distance test (params=None only)."""
+        return bool(lib().faiss_amd_IndexHNSW_check_relative_distance(self.h))
+
+    @check_relative_distance.setter
+    def check_relative_distance(self, v):
+        lib().faiss_amd_IndexHNSW_set_check_relative_distance(self.h, int(bool(v)))
+
+    @property
+    def search_bounded_queue(self):
+        """hnsw.search_bounded_queue: False searches level 0 with the
+        unbounded candidate queue (params=None only)."""
+        return bool(lib().faiss_amd_IndexHNSW_search_bounded_queue(self.h))
+
+    @search_bounded_queue.setter
+    def search_bounded_queue(self, v):
+        lib().faiss_amd_IndexHNSW_set_search_bounded_queue(self.h, int(bool(v)))
+
+    @property
     def efConstruction(self):
         return lib().faiss_amd_IndexHNSW_efConstruction(self.h)
 
@@ -450,15 +484,16 @@ class IndexHNSW(Index):
     def efConstruction(self, v):
         lib().faiss_amd_IndexHNSW_set_efConstruction(self.h, int(v))
 
-    def search_stats(self, x, k):
+    def search_stats(self, x, k, params=None):
         """IndexHNSW::search_stats: (D, I, per-query QueryLatencyStats records)."""
         x = _f32(x)
         n = x.shape[0]
         D = np.empty((n, k), dtype=np.float32)
         I = np.empty((n, k), dtype=np.int64)
         st = np.zeros(n, dtype=QUERY_LATENCY_DTYPE)
-        _check(lib().faiss_amd_IndexHNSW_search_stats(self.h, n, _ptr(x), k, None, _ptr(D),
-                                                      _ptr(I), _ptr(st)))
+        _check(lib().faiss_amd_IndexHNSW_search_stats(self.h, n, _ptr(x), k,
+                                                      params.h if params is not None else None,
+                                                      _ptr(D), _ptr(I), _ptr(st)))
         return D, I, st
 
     def storage_vectors(self):
@@ -872,14 +907,45 @@ def IDSelectorXOr(a, b):
     return _sel_binary(lib().faiss_IDSelectorXOr_new, a, b)
 
 
+class SearchParametersHNSW:
+    """faiss.SearchParametersHNSW.  Passed to a search it replaces the index's
+    own efSearch, check_relative_distance and search_bounded_queue altogether
+    (fields left alone keep these defaults, as in the reference).  sel filters
+    the results, not the traversal; bounded_queue=False ignores it and
+    check_relative_distance."""
+
+    def __init__(self, efSearch=16, check_relative_distance=True, bounded_queue=True, sel=None):
+        p = C.c_void_p()
+        _check(lib().faiss_amd_SearchParametersHNSW_new(
+            C.byref(p), int(efSearch), int(bool(check_relative_distance)),
+            int(bool(bounded_queue)), sel.h if sel else None))
+        self.h = p
+        self.efSearch = int(efSearch)
+        self.check_relative_distance = bool(check_relative_distance)
+        self.bounded_queue = bool(bounded_queue)
+        self.sel = sel  # must outlive the searches that use it
+
+    def __del__(self):
+        try:
+            lib().faiss_amd_SearchParametersHNSW_free(self.h)
+        except Exception:
+            pass
+
+
 class SearchParametersIVF:
-    def __init__(self, nprobe=1, max_codes=0, quantizer_efSearch=0, sel=None):
+    def __init__(self, nprobe=1, max_codes=0, quantizer_efSearch=0, sel=None,
+                 quantizer_params=None):
         p = C.c_void_p()
         _check(lib().faiss_SearchParametersIVF_new_with(C.byref(p), sel.h if sel else None,
                                                         nprobe, max_codes))
         self.h = p
         self._sel = sel
-        if quantizer_efSearch:
+        self.quantizer_params = quantizer_params  # must outlive the searches that use it
+        if quantizer_params is not None:
+            if quantizer_efSearch:
+                raise ValueError("give quantizer_params or quantizer_efSearch, not both")
+            lib().faiss_amd_SearchParametersIVF_set_quantizer_params(self.h, quantizer_params.h)
+        elif quantizer_efSearch:
             lib().faiss_amd_SearchParametersIVF_set_quantizer_efSearch(self.h,
                                                                        int(quantizer_efSearch))
 

@@ -31,6 +31,9 @@ struct SearchParamsC {
 struct RefineParamsC {
     IndexRefineSearchParameters refine;
 };
+struct HnswParamsC {
+    SearchParametersHNSW hnsw;
+};
 
 inline Index* IX(FaissIndex* p) { return reinterpret_cast<Index*>(p); }
 inline const Index* IX(const FaissIndex* p) { return reinterpret_cast<const Index*>(p); }
@@ -98,11 +101,13 @@ int faiss_Index_search(const FaissIndex* index, idx_t n, const float* x, idx_t k
 }
 
 // every FaissSearchParameters* points at an object whose first member is the
-// C++ parameter object: SearchParamsC (ivf) or RefineParamsC (refine)
+// C++ parameter object: SearchParamsC (ivf), RefineParamsC (refine) or
+// HnswParamsC (hnsw)
 static const SearchParameters* resolve_params(const FaissSearchParameters* p) {
     if (!p) return nullptr;
     auto base = reinterpret_cast<const SearchParameters*>(p);
     if (dynamic_cast<const IndexRefineSearchParameters*>(base)) return base;
+    if (dynamic_cast<const SearchParametersHNSW*>(base)) return base;
     auto sp = reinterpret_cast<const SearchParamsC*>(p);
     return &sp->ivf;
 }
@@ -251,6 +256,41 @@ void faiss_amd_SearchParametersIVF_set_quantizer_efSearch(FaissSearchParametersI
     } else {
         sp->ivf.quantizer_params = nullptr;
     }
+}
+// every field of the quantizer's SearchParametersHNSW (the reference passes
+// the object: fields left alone keep the struct's defaults, not the index's)
+void faiss_amd_SearchParametersIVF_set_quantizer_hnsw(FaissSearchParametersIVF* p, int efSearch,
+                                                      int check_relative_distance,
+                                                      int bounded_queue) {
+    auto sp = reinterpret_cast<SearchParamsC*>(p);
+    sp->hnsw.efSearch = efSearch;
+    sp->hnsw.check_relative_distance = check_relative_distance != 0;
+    sp->hnsw.bounded_queue = bounded_queue != 0;
+    sp->ivf.quantizer_params = &sp->hnsw;
+}
+// SearchParametersHNSW for faiss_Index_search_with_params on an IndexHNSW (the
+// reference's C API has none); sel may be null and is not owned
+int faiss_amd_SearchParametersHNSW_new(FaissSearchParameters** p_sp, int efSearch,
+                                       int check_relative_distance, int bounded_queue,
+                                       FaissIDSelector* sel) {
+    C_TRY auto sp = new HnswParamsC();
+    sp->hnsw.efSearch = efSearch;
+    sp->hnsw.check_relative_distance = check_relative_distance != 0;
+    sp->hnsw.bounded_queue = bounded_queue != 0;
+    sp->hnsw.sel = reinterpret_cast<IDSelector*>(sel);
+    *p_sp = reinterpret_cast<FaissSearchParameters*>(sp);
+    C_CATCH
+}
+void faiss_amd_SearchParametersHNSW_free(FaissSearchParameters* obj) {
+    delete reinterpret_cast<HnswParamsC*>(obj);
+}
+// SearchParametersIVF::quantizer_params = any parameter object of this API
+// (not owned; it must outlive the searches; null: none) — the form that
+// carries a quantizer selector
+void faiss_amd_SearchParametersIVF_set_quantizer_params(FaissSearchParametersIVF* p,
+                                                        FaissSearchParameters* qparams) {
+    reinterpret_cast<SearchParamsC*>(p)->ivf.quantizer_params =
+            const_cast<SearchParameters*>(resolve_params(qparams));
 }
 
 // ---------------- IndexFlat
@@ -639,6 +679,20 @@ int faiss_amd_IndexHNSW_efSearch(const FaissIndexHNSW* p) {
 void faiss_amd_IndexHNSW_set_efSearch(FaissIndexHNSW* p, int v) {
     if (auto h = HNnt(p)) h->hnsw.efSearch = v;
 }
+int faiss_amd_IndexHNSW_check_relative_distance(const FaissIndexHNSW* p) {
+    auto h = HNnt(p);
+    return h && h->hnsw.check_relative_distance ? 1 : 0;
+}
+void faiss_amd_IndexHNSW_set_check_relative_distance(FaissIndexHNSW* p, int v) {
+    if (auto h = HNnt(p)) h->hnsw.check_relative_distance = v != 0;
+}
+int faiss_amd_IndexHNSW_search_bounded_queue(const FaissIndexHNSW* p) {
+    auto h = HNnt(p);
+    return h && h->hnsw.search_bounded_queue ? 1 : 0;
+}
+void faiss_amd_IndexHNSW_set_search_bounded_queue(FaissIndexHNSW* p, int v) {
+    if (auto h = HNnt(p)) h->hnsw.search_bounded_queue = v != 0;
+}
 int faiss_amd_IndexHNSW_efConstruction(const FaissIndexHNSW* p) {
     auto h = HNnt(p);
     return h ? h->hnsw.efConstruction : 0;
@@ -655,11 +709,15 @@ int faiss_amd_IndexHNSW_search_stats(const FaissIndexHNSW* p, idx_t n, const flo
                                      idx_t* labels, FaissQueryLatencyStats* per_query_stats) {
     C_TRY auto h = HNnt(p);
     FAISS_THROW_IF_NOT_MSG(h, "index is not an IndexHNSW");
-    // the efSearch set with faiss_amd_SearchParametersIVF_set_quantizer_efSearch
+    // a faiss_amd_SearchParametersHNSW_new object, or the quantizer params
+    // set on a FaissSearchParametersIVF (…_set_quantizer_efSearch / _hnsw)
     const SearchParameters* sp = nullptr;
     if (params) {
-        auto c = reinterpret_cast<const SearchParamsC*>(params);
-        if (c->ivf.quantizer_params) sp = &c->hnsw;
+        sp = resolve_params(params);
+        if (!dynamic_cast<const SearchParametersHNSW*>(sp)) {
+            auto c = reinterpret_cast<const SearchParamsC*>(params);
+            sp = c->ivf.quantizer_params ? &c->hnsw : nullptr;
+        }
     }
     h->search_stats(n, x, k, distances, labels, sp,
                     reinterpret_cast<QueryLatencyStats*>(per_query_stats));
@@ -939,6 +997,18 @@ int faiss_amd_Index_search_device(const FaissIndex* index, idx_t n, const float*
     ensure_hip();
     ix->sync_device();
     ix->search_device(n, x_dev, ldx_of(ix), k, d_dev, l_dev, nullptr, pick_stream(ix, stream));
+    C_CATCH
+}
+int faiss_amd_Index_search_device_with_params(const FaissIndex* index, idx_t n,
+                                              const float* x_dev, idx_t k,
+                                              const FaissSearchParameters* params, float* d_dev,
+                                              idx_t* l_dev, void* stream) {
+    C_TRY const Index* ix = IX(index);
+    FAISS_THROW_IF_NOT_MSG(ix->d % 4 == 0, "device entry points need d % 4 == 0");
+    ensure_hip();
+    ix->sync_device();
+    ix->search_device(n, x_dev, ldx_of(ix), k, d_dev, l_dev, resolve_params(params),
+                      pick_stream(ix, stream));
     C_CATCH
 }
 int faiss_amd_IndexIVF_search_preassigned_device(const FaissIndexIVF* index, idx_t n,

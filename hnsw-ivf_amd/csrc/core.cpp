@@ -453,6 +453,20 @@ void IndexFlat::search_device(idx_t n, const float* x, int ldx, idx_t k, float* 
     knn_device<idx_t>(n, x, ldx, (int)k, distances, labels, s);
 }
 
+const idx_t* IndexFlat::device_row_ids(hipStream_t s) const {
+    std::lock_guard<std::recursive_mutex> g(mu_);
+    if (selids_n_ != ntotal) {
+        std::vector<idx_t> iota((size_t)ntotal);
+        for (idx_t i = 0; i < ntotal; i++) iota[(size_t)i] = i;
+        s_selids_.reserve(sizeof(idx_t) * ntotal);
+        HIP_CHECK(hipMemcpyAsync(s_selids_.ptr, iota.data(), sizeof(idx_t) * ntotal,
+                                 hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));  // (iota is a host temporary)
+        selids_n_ = ntotal;
+    }
+    return s_selids_.as<idx_t>();
+}
+
 void IndexFlat::search_selected(idx_t n, const float* x, int ldx, idx_t k, float* distances,
                                 idx_t* labels, const IDSelector* sel, hipStream_t s) const {
     FAISS_THROW_IF_NOT_FMT(k >= 1, "k = %lld must be >= 1", (long long)k);
@@ -479,17 +493,9 @@ void IndexFlat::search_selected(idx_t n, const float* x, int ldx, idx_t k, float
         // knn_*_by_idx visits the array in its own order, which differs
         // only for an array that lists an id twice or under distance ties)
         direct = true;
-        if (selids_n_ != ntotal) {
-            std::vector<idx_t> iota((size_t)ntotal);
-            for (idx_t i = 0; i < ntotal; i++) iota[(size_t)i] = i;
-            s_selids_.reserve(sizeof(idx_t) * ntotal);
-            HIP_CHECK(hipMemcpyAsync(s_selids_.ptr, iota.data(), sizeof(idx_t) * ntotal,
-                                     hipMemcpyHostToDevice, s));
-            HIP_CHECK(hipStreamSynchronize(s));  // (iota is a host temporary)
-            selids_n_ = ntotal;
-        }
+        const idx_t* ids = device_row_ids(s);
         s_selmask_.reserve((size_t)ntotal);
-        sel->mark_device(s_selids_.as<idx_t>(), ntotal, s_selmask_.as<uint8_t>(), s);
+        sel->mark_device(ids, ntotal, s_selmask_.as<uint8_t>(), s);
         mask = s_selmask_.as<uint8_t>();
     }
     if (metric_l2 && !direct && ny > 0) {

@@ -438,21 +438,50 @@ void IndexHNSW::sync_device() const {
     dirty_ = false;
 }
 
+IndexHNSW::SearchMode IndexHNSW::search_mode(const SearchParameters* params) const {
+    // faiss/IndexHNSW.cpp:258-266; faiss/impl/HNSW.cpp:619-622, :954-955, :967
+    SearchMode m;
+    if (params) {
+        auto p = dynamic_cast<const SearchParametersHNSW*>(params);
+        FAISS_THROW_IF_NOT_MSG(p, "params type invalid");
+        m.efSearch = p->efSearch;
+        m.check_relative_distance = p->check_relative_distance;
+        m.bounded_queue = p->bounded_queue;
+        m.sel = p->sel;
+    } else {
+        m.efSearch = hnsw.efSearch;
+        m.check_relative_distance = hnsw.check_relative_distance;
+        m.bounded_queue = hnsw.search_bounded_queue;
+    }
+    if (!m.bounded_queue) {  // search_from_candidate_unbounded takes no params
+        m.check_relative_distance = true;
+        m.sel = nullptr;
+    }
+    return m;
+}
+
 template <class OutIdx>
 void IndexHNSW::hnsw_device(idx_t n, const float* x, int ldx, int k, float* distances,
                             OutIdx* labels, const SearchParameters* params, hipStream_t s,
                             bool defer) const {
     // faiss/IndexHNSW.cpp:246-343 (hnsw_search)
     FAISS_THROW_IF_NOT(k > 0);
-    int efSearch = hnsw.efSearch;
-    if (params) {
-        auto p = dynamic_cast<const SearchParametersHNSW*>(params);
-        FAISS_THROW_IF_NOT_MSG(p, "params type invalid");
-        efSearch = p->efSearch;
-    }
+    const SearchMode sm = search_mode(params);
+    const int efSearch = sm.efSearch;
     sync_device();
     std::lock_guard<std::recursive_mutex> g(mu_);
     order_.enter(s);
+    kern::HNSWMode mode;
+    mode.check_relative_distance = sm.check_relative_distance;
+    mode.bounded_queue = sm.bounded_queue;
+    if (sm.sel && ntotal > 0) {
+        // the selector over the nodes 0 .. ntotal - 1 (the storage's rows),
+        // one byte each, in s_rlog_: a selector keeps the register kernel,
+        // the only user of the replay logs, away (rlog below is false)
+        s_rlog_.reserve((size_t)ntotal);
+        sm.sel->mark_device(storage->device_row_ids(s), ntotal, s_rlog_.as<uint8_t>(), s);
+        mode.mask = s_rlog_.as<uint8_t>();
+    }
     kern::HNSWDevice gd;
     gd.storage = storage->device_vectors();
     gd.norms = nullptr;
@@ -482,8 +511,8 @@ void IndexHNSW::hnsw_device(idx_t n, const float* x, int ldx, int k, float* dist
     // queries per launch: the per-query visited bitmaps that do not fit in
     // LDS, and heaps beyond it (max(efSearch, k) in the thousands), live in
     // scratch kept under 256 MiB each (chunks of the batch)
-    const size_t hw = kern::hnsw_heap_scratch_words(k, efSearch, ld());
-    const bool scratch = kern::hnsw_visited_scratch_needed(ld(), k, efSearch, vwords);
+    const size_t hw = kern::hnsw_heap_scratch_words(k, efSearch, ld(), mode, ntotal);
+    const bool scratch = kern::hnsw_visited_scratch_needed(ld(), k, efSearch, vwords, mode);
     idx_t qc = n;
     if (scratch)
         qc = std::min<idx_t>(qc, std::max<idx_t>(1, (idx_t)(((size_t)256 << 20) /
@@ -492,8 +521,9 @@ void IndexHNSW::hnsw_device(idx_t n, const float* x, int ldx, int k, float* dist
     // the register kernel's replay logs (kHnswReplayCap entries per query)
     // (FAISS_AMD_HNSW_REPLAY=0: none; such queries search level 0 again — A/B)
     const char* renv = getenv("FAISS_AMD_HNSW_REPLAY");
-    const bool rlog = kern::hnsw_register_eligible(k, efSearch) &&
-                      !kern::hnsw_uses_batched(k, efSearch) && !(renv && !strcmp(renv, "0"));
+    const bool rlog = kern::hnsw_register_eligible(k, efSearch, mode) &&
+                      !kern::hnsw_uses_batched(k, efSearch, mode) && !(renv && !strcmp(renv, "0"));
+    FAISS_THROW_IF_NOT(!rlog || !mode.mask);  // (s_rlog_ holds one or the other)
     // FAISS_AMD_HNSW_REPLAY_CAP=<entries>: a smaller log per query (tests: the
     // overflow path)
     int64_t rcap = kern::kHnswReplayCap;
@@ -511,8 +541,9 @@ void IndexHNSW::hnsw_device(idx_t n, const float* x, int ldx, int k, float* dist
     const size_t alb = kern::hnsw_arrival_log_bytes(qc, ntotal);
     s_alog_.reserve(alb);
     s_flags_.reserve(sizeof(uint32_t) * std::max<idx_t>(qc, 1));
-    // defer (split_begin): one chunk, the batched kernel in use
-    defer = defer && !scratch && !hw && i32 && kern::hnsw_uses_batched(k, efSearch);
+    // defer (split_begin): one chunk, the batched kernel in use (the default
+    // mode only: hnsw_uses_batched is false for any other)
+    defer = defer && !scratch && !hw && i32 && kern::hnsw_uses_batched(k, efSearch, mode);
     for (idx_t q0 = 0; q0 < n; q0 += qc) {
         const idx_t nq = std::min(qc, n - q0);
         kern::hnsw_search(gd, x + q0 * ldx, ldx, nq, k, efSearch, distances + q0 * k,
@@ -521,7 +552,7 @@ void IndexHNSW::hnsw_device(idx_t n, const float* x, int ldx, int k, float* dist
                           vwords, d_stats_.as<unsigned long long>(), s_flags_.as<uint32_t>(), s,
                           &ktimes, defer, hw ? s_heaps_.as<float>() : nullptr,
                           rlog ? s_rlog_.as<uint64_t>() : nullptr, rlog ? rcap : 0, s_alog_.ptr,
-                          alb);
+                          alb, mode);
     }
     if (!defer) {
         order_.leave(s);
@@ -687,8 +718,6 @@ void IndexHNSW::search_stats(idx_t n, const float* x, idx_t k, float* distances,
 void IndexHNSW::search_device(idx_t n, const float* x, int ldx, idx_t k, float* distances,
                               idx_t* labels, const SearchParameters* params,
                               hipStream_t s) const {
-    FAISS_THROW_IF_NOT_MSG(!params || !params->sel,
-                           "IDSelector is supported by the IVF indexes only on this path");
     DevGuard2 dg(device);
     hnsw_device<idx_t>(n, x, ldx, (int)k, distances, labels, params, s);
 }

@@ -715,9 +715,14 @@ bool IndexIVF::scan_hnsw_pipelined(idx_t nq, const float* x, int ldx, idx_t k, i
                                    const SearchParameters* qparams, hipStream_t s) const {
     const auto* qh = dynamic_cast<const IndexHNSW*>(quantizer);
     if (!qh || qdone_ || get_search_slices() > 1) return false;
-    int ef = qh->hnsw.efSearch;
-    if (const auto* hp = dynamic_cast<const SearchParametersHNSW*>(qparams)) ef = hp->efSearch;
-    if (!kern::hnsw_register_eligible(np, ef) || kern::hnsw_uses_batched(np, ef)) return false;
+    // (the register kernel serves the default search mode only; any other
+    // mode or a quantizer selector takes the plain assignment)
+    if (qparams && !dynamic_cast<const SearchParametersHNSW*>(qparams)) return false;
+    const IndexHNSW::SearchMode qm = qh->search_mode(qparams);
+    const int ef = qm.efSearch;
+    if (!qm.is_default() || !kern::hnsw_register_eligible(np, ef) ||
+        kern::hnsw_uses_batched(np, ef))
+        return false;
     const char* env = getenv("FAISS_AMD_HNSW_PIPE");
     const int P = env ? atoi(env) : 1;  // off: measured slower on c4 (below)
     if (P <= 1 || nq < (idx_t)P * 1024) return false;

@@ -410,6 +410,19 @@ struct HNSWDevice {
     int max_level;
     int ntotal;
 };
+// The level-0 search mode (faiss/impl/HNSW.cpp:619-622, :954-955) and the
+// result selector.  The default mode (bounded queue, relative-distance stop,
+// no selector) is what the register, batched and wide kernels implement; any
+// other runs the sequential kernel (k_hnsw_exact: the stop after efSearch
+// level-0 hops, mask gating the result heap) or, with bounded_queue false,
+// k_hnsw_unbounded (search_from_candidate_unbounded, :744-848; it reads
+// neither check_relative_distance nor mask, as the reference does not).
+struct HNSWMode {
+    bool check_relative_distance = true;
+    bool bounded_queue = true;
+    const uint8_t* mask = nullptr;  // [ntotal] 1 = member; null: every node
+    bool is_default() const { return check_relative_distance && bounded_queue && !mask; }
+};
 // reference faiss/impl/HNSW.cpp:943-996 (HNSW::search), :852-924 (greedy),
 // :605-741 (search_from_candidates), :1096-1342 (MinimaxHeap)
 // flags: [n] scratch; queries where an exact distance tie makes the batched
@@ -424,7 +437,8 @@ void hnsw_search(const HNSWDevice& g, const float* x, int ldx, int64_t n, int k,
                  hipStream_t s, KernelTimes* kt = nullptr,
                  bool defer = false, float* heap_scratch = nullptr,
                  uint64_t* replay_log = nullptr, int64_t replay_cap = 0,
-                 void* arrival_log = nullptr, size_t arrival_log_bytes = 0);
+                 void* arrival_log = nullptr, size_t arrival_log_bytes = 0,
+                 const HNSWMode& mode = HNSWMode{});
 // the register kernel's CandSet update log (64-bit entries per query in
 // replay_log): a query whose candidate set meets a layout-dependent decision
 // continues from a replayed heap instead of searching level 0 again; a query
@@ -436,18 +450,22 @@ void hnsw_search(const HNSWDevice& g, const float* x, int ldx, int64_t n, int k,
 constexpr int64_t kHnswReplayCap = 1024;
 constexpr int kHnswStatsWords = 9;
 // 32-bit words of global heap scratch per query (0: the heaps fit the LDS)
-size_t hnsw_heap_scratch_words(int k, int efSearch, int ld);
+// (bounded_queue false: both queues of k_hnsw_unbounded, any number of pushes)
+size_t hnsw_heap_scratch_words(int k, int efSearch, int ld, const HNSWMode& mode = HNSWMode{},
+                               int64_t ntotal = 0);
 // a per-query visited bitmap of vwords words lives in global scratch (for
 // some kernel this search may run) rather than the LDS
-bool hnsw_visited_scratch_needed(int ld, int k, int efSearch, int64_t vwords);
-// the register kernel serves max(efSearch, k) <= 64
-bool hnsw_register_eligible(int k, int efSearch);
+bool hnsw_visited_scratch_needed(int ld, int k, int efSearch, int64_t vwords,
+                                 const HNSWMode& mode = HNSWMode{});
+// the register kernel serves max(efSearch, k) <= 64 (default mode only, as
+// the batched and wide kernels: all three are false for any other mode)
+bool hnsw_register_eligible(int k, int efSearch, const HNSWMode& mode = HNSWMode{});
 // the batched kernel (and its tie re-runs) runs for these parameters
-bool hnsw_uses_batched(int k, int efSearch);  // leave the flagged queries to the caller
+bool hnsw_uses_batched(int k, int efSearch, const HNSWMode& mode = HNSWMode{});  // leave the flagged queries to the caller
 // 128 < max(efSearch, k) <= kHnswWideMaxEf: the wide kernel (k_hnsw_wide,
 // candidate set sorted in the LDS) + sequential re-runs of its flagged queries
 constexpr int kHnswWideMaxEf = 4096;
-bool hnsw_uses_wide(int k, int efSearch);
+bool hnsw_uses_wide(int k, int efSearch, const HNSWMode& mode = HNSWMode{});
 // flagged queries (flags[q] != 0) -> idx[0 .. *count) (count zeroed first)
 void hnsw_flag_compact(const uint32_t* flags, int64_t n, uint32_t* idx, uint32_t* count,
                        hipStream_t s);
@@ -456,7 +474,8 @@ void hnsw_flag_compact(const uint32_t* flags, int64_t n, uint32_t* idx, uint32_t
 void hnsw_exact_listed(const HNSWDevice& g, const float* x, int ldx, const uint32_t* qidx,
                        int64_t nf, int k, int efSearch, float* D, int32_t* I32,
                        uint32_t* visited_scratch, int64_t vwords, unsigned long long* stats,
-                       hipStream_t s, void* arrival_log = nullptr, size_t arrival_log_bytes = 0);
+                       hipStream_t s, void* arrival_log = nullptr, size_t arrival_log_bytes = 0,
+                       const HNSWMode& mode = HNSWMode{});
 // bytes of the sequential kernel's arrival-log pool (k_hnsw_exact without
 // the result heap) worth providing for n queries of an ntotal-node graph
 size_t hnsw_arrival_log_bytes(int64_t n, int64_t ntotal);

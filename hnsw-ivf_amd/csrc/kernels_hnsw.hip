@@ -457,6 +457,87 @@ __device__ __forceinline__ void sx_push(uint64_t* b, int n, uint64_t val, int la
     if (j <= m) b[n >> (j - 1)] = a;
     if (lane == 0) b[n >> m] = val;
 }
+
+// greedy descent over the levels above 0 (HNSW.cpp:852-924), as in
+// k_hnsw_search: from the entry point to level 0's seed (nearest, d_nearest)
+__device__ __forceinline__ void seq_greedy(const HNSWDevice& g, const float* qs, int lane,
+                                           int& nearest, float& d_nearest, uint32_t& st_ndis,
+                                           uint32_t& st_nhops) {
+    d_nearest = l2_row(qs, g.storage + (int64_t)nearest * g.ld, g.d);
+    for (int level = g.max_level; level >= 1; level--) {
+        for (;;) {
+            const uint64_t o = g.offsets[nearest];
+            const int b = g.cum_nb[level], e = g.cum_nb[level + 1];
+            const int cnt = e - b;
+            int v = lane < cnt ? g.neighbors[o + b + lane] : -1;
+            unsigned long long neg =
+                    __ballot(lane < cnt && v < 0) | (cnt < 64 ? (~0ull << cnt) : 0ull);
+            const int first_neg = neg ? __ffsll((long long)neg) - 1 : 64;
+            float dis = WS_INF;
+            if (lane < first_neg) dis = l2_row(qs, g.storage + (int64_t)v * g.ld, g.d);
+            st_ndis += (uint32_t)min(first_neg, 64);
+            st_nhops += 1;
+            float md = dis;
+            int ml = lane;
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) {
+                const float od = __shfl_xor(md, m);
+                const int ol = __shfl_xor(ml, m);
+                if (od < md || (od == md && ol < ml)) {
+                    md = od;
+                    ml = ol;
+                }
+            }
+            if (md < d_nearest) {
+                d_nearest = md;
+                nearest = __shfl(v, ml);
+            } else {
+                break;
+            }
+        }
+    }
+}
+
+// One level-0 hop's arrivals: the neighbours of v0 in stored order up to the
+// first -1, visited test-and-set in that order (neighbour j is fresh when its
+// bit was clear before this hop and no earlier neighbour of the list is the
+// same node; the fresh ones keep their stored order).  Lane t < nf returns
+// the t-th fresh node (fv) and its distance (fdis), 4 lanes per row in the
+// reference order for d <= 128.
+__device__ __forceinline__ int seq_fresh_rows(const HNSWDevice& g, const float* qs, uint32_t* vis,
+                                              int32_t v0, int cnt, int lane, int32_t& fv,
+                                              float& fdis) {
+    int32_t v1 = -1;
+    if (lane < cnt)
+        v1 = g.nb0 ? g.nb0[(int64_t)v0 * g.nb0_stride + lane]
+                   : g.neighbors[g.offsets[v0] + g.cum_nb[0] + lane];
+    const unsigned long long neg =
+            __ballot(lane < cnt && v1 < 0) | (cnt < 64 ? (~0ull << cnt) : 0ull);
+    const int jmax = neg ? __ffsll((long long)neg) - 1 : 64;
+    // (the bits as they were before this hop decide; a node listed twice —
+    // the atomic then finds the bit another lane of this hop set — is visited
+    // at its first position, so only then the lanes are compared pairwise)
+    const uint32_t vbit = 1u << (v1 & 31);
+    bool fresh = lane < jmax && !(vis[v1 >> 5] & vbit);
+    uint32_t old = 0u;
+    if (fresh) old = atomicOr(&vis[v1 >> 5], vbit);
+    if (__ballot(fresh && (old & vbit)) != 0ull)
+        for (int i = 0; i < jmax; i++)
+            fresh &= !(i < lane && __builtin_amdgcn_readlane(v1, i) == v1);
+    const unsigned long long fm = __ballot(fresh);
+    const int nf = __popcll(fm);
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const int dst = fresh ? __popcll(fm & lt) : nf + __popcll(~fm & lt);
+    fv = __builtin_amdgcn_ds_permute(dst << 2, v1);
+    // the fresh rows, 4 lanes per row (reference order)
+    fdis = 0.f;
+    if (g.d <= 128)
+        fdis = ref_rows64_4lane_pb<true, 16, 1>(qs, qs, g.storage, g.ld, g.d,
+                                                lane < nf ? (uint32_t)fv : 0u, nf, lane);
+    else if (lane < nf)
+        fdis = l2_row(qs, g.storage + (int64_t)fv * g.ld, g.d);
+    return nf;
+}
 }  // namespace
 
 // HNSW::search with the reference's own data structures, operation for
@@ -476,13 +557,19 @@ __device__ __forceinline__ void sx_push(uint64_t* b, int n, uint64_t val, int la
 // of k_hnsw_exact, also run in place by k_hnsw_wide<.., INPLACE> for the
 // queries it flags.  blk: the work group's slot of the global heaps and
 // visited words; sm: the work group's dynamic LDS (seq_lds_bytes + visited).
-template <bool LDS_VISITED, bool GH>
+// EXT: the non-default forms of search_from_candidates (:619-622) — check_rel
+// false replaces the count_below stop by the stop after efSearch level-0 hops
+// (:645-654, :725-728); mask (one byte per node, null: every node) is the
+// selector, which gates res.add_result alone (:629, :677), so it is read for
+// the seed and for arrivals under the result threshold only.  The arrival log
+// takes members only, since its results are selected from the log.
+template <bool LDS_VISITED, bool GH, bool EXT = false>
 __device__ __forceinline__ void hnsw_exact_query(
         HNSWDevice g, const float* __restrict__ x, int ldx, int k, int efSearch, int ef,
         float* __restrict__ D, int64_t* __restrict__ I, int32_t* __restrict__ I32,
         uint32_t* __restrict__ vis_global, int64_t vwords, unsigned long long* __restrict__ stats,
         float* __restrict__ gheap, ArrivalLog alog, int64_t q, int64_t qo, int64_t blk,
-        float* sm) {
+        float* sm, bool check_rel = true, const uint8_t* __restrict__ mask = nullptr) {
     const int qpad = seq_qpad(g.ld);
     float* qs = sm;  // [qpad]
     uint64_t* cb = GH ? (uint64_t*)((char*)gheap + blk * seq_heap_bytes(ef, k))
@@ -511,39 +598,8 @@ __device__ __forceinline__ void hnsw_exact_query(
     if (g.entry_point >= 0) {
         // ---- greedy descent (HNSW.cpp:852-924), as in k_hnsw_search
         int nearest = g.entry_point;
-        float d_nearest = l2_row(qs, g.storage + (int64_t)nearest * g.ld, g.d);
-        for (int level = g.max_level; level >= 1; level--) {
-            for (;;) {
-                const uint64_t o = g.offsets[nearest];
-                const int b = g.cum_nb[level], e = g.cum_nb[level + 1];
-                const int cnt = e - b;
-                int v = lane < cnt ? g.neighbors[o + b + lane] : -1;
-                unsigned long long neg =
-                        __ballot(lane < cnt && v < 0) | (cnt < 64 ? (~0ull << cnt) : 0ull);
-                const int first_neg = neg ? __ffsll((long long)neg) - 1 : 64;
-                float dis = WS_INF;
-                if (lane < first_neg) dis = l2_row(qs, g.storage + (int64_t)v * g.ld, g.d);
-                st_ndis += (uint32_t)min(first_neg, 64);
-                st_nhops += 1;
-                float md = dis;
-                int ml = lane;
-#pragma unroll
-                for (int m = 32; m > 0; m >>= 1) {
-                    const float od = __shfl_xor(md, m);
-                    const int ol = __shfl_xor(ml, m);
-                    if (od < md || (od == md && ol < ml)) {
-                        md = od;
-                        ml = ol;
-                    }
-                }
-                if (md < d_nearest) {
-                    d_nearest = md;
-                    nearest = __shfl(v, ml);
-                } else {
-                    break;
-                }
-            }
-        }
+        float d_nearest = 0.f;
+        seq_greedy(g, qs, lane, nearest, d_nearest, st_ndis, st_nhops);
         // ---- level 0: MinimaxHeap candidates(ef) seeded with the entry;
         // search_from_candidates (:624-637): the seed enters the results
         int hk = 1, nvalid = 1;
@@ -553,10 +609,14 @@ __device__ __forceinline__ void hnsw_exact_query(
         }
         __syncthreads();
         float rthr = sx_dis(rb[1]);
+        const bool seed_in = !EXT || !mask || mask[nearest] != 0;
+        int l0steps = 0;  // nstep of search_from_candidates (st_nhops has the greedy hops too)
         if (lg) {
-            if (lane == 0) lg[0] = sx_key(d_nearest, nearest);
-            lpos = 1;
-        } else if (d_nearest < rthr) {
+            if (seed_in) {
+                if (lane == 0) lg[0] = sx_key(d_nearest, nearest);
+                lpos = 1;
+            }
+        } else if (seed_in && d_nearest < rthr) {
             sx_sift(rb, k, sx_key(d_nearest, nearest), lane);
             rthr = sx_dis(rb[1]);
         }
@@ -629,44 +689,14 @@ __device__ __forceinline__ void hnsw_exact_query(
 #endif
             if (lane == 0) cb[bp] = sx_key(d0, -1);
             nvalid--;
-            if (nb >= efSearch) {
+            if ((!EXT || check_rel) && nb >= efSearch) {
                 st_n2 = nvalid == 0 ? 1u : 0u;
                 break;
             }
-            // neighbours of v0 in stored order; visited test-and-set in order
-            // (neighbour j is fresh when its bit was clear before this hop and
-            // no earlier neighbour of the list is the same node; the fresh
-            // ones keep their stored order)
-            int32_t v1 = -1;
-            if (lane < cnt)
-                v1 = g.nb0 ? g.nb0[(int64_t)v0 * g.nb0_stride + lane]
-                           : g.neighbors[g.offsets[v0] + g.cum_nb[0] + lane];
-            const unsigned long long neg =
-                    __ballot(lane < cnt && v1 < 0) | (cnt < 64 ? (~0ull << cnt) : 0ull);
-            const int jmax = neg ? __ffsll((long long)neg) - 1 : 64;
-            // (the bits as they were before this hop decide; a node listed
-            // twice — the atomic then finds the bit another lane of this hop
-            // set — is visited at its first position, so only then the lanes
-            // are compared pairwise)
-            const uint32_t vbit = 1u << (v1 & 31);
-            bool fresh = lane < jmax && !(vis[v1 >> 5] & vbit);
-            uint32_t old = 0u;
-            if (fresh) old = atomicOr(&vis[v1 >> 5], vbit);
-            if (__ballot(fresh && (old & vbit)) != 0ull)
-                for (int i = 0; i < jmax; i++)
-                    fresh &= !(i < lane && __builtin_amdgcn_readlane(v1, i) == v1);
-            const unsigned long long fm = __ballot(fresh);
-            const int nf = __popcll(fm);
-            const unsigned long long lt = (1ull << lane) - 1ull;
-            const int dst = fresh ? __popcll(fm & lt) : nf + __popcll(~fm & lt);
-            const int32_t fv = __builtin_amdgcn_ds_permute(dst << 2, v1);
-            // the fresh rows, 4 lanes per row (reference order)
-            float fdis = 0.f;
-            if (g.d <= 128)
-                fdis = ref_rows64_4lane_pb<true, 16, 1>(qs, qs, g.storage, g.ld, g.d,
-                                                        lane < nf ? (uint32_t)fv : 0u, nf, lane);
-            else if (lane < nf)
-                fdis = l2_row(qs, g.storage + (int64_t)fv * g.ld, g.d);
+            // the fresh neighbours of v0 in arrival order and their distances
+            int32_t fv;
+            float fdis;
+            const int nf = seq_fresh_rows(g, qs, vis, v0, cnt, lane, fv, fdis);
             st_ndis += (uint32_t)nf;
             st_nhops += 1;
             // add_to_heap (:678-689) in arrival order; an arrival that can
@@ -674,15 +704,26 @@ __device__ __forceinline__ void hnsw_exact_query(
             // full candidate heap's top) changes nothing
             uint64_t top = hk == ef ? cb[1] : 0ull;  // the full heap's top
             if (lg) {  // the hop's arrivals, in order
-                if (lane < nf) lg[lpos + lane] = sx_key(fdis, fv);
-                lpos += nf;
+                if (EXT && mask) {
+                    const bool in = lane < nf && mask[fv] != 0;
+                    const unsigned long long im = __ballot(in);
+                    if (in) lg[lpos + __popcll(im & ((1ull << lane) - 1ull))] = sx_key(fdis, fv);
+                    lpos += __popcll(im);
+                } else {
+                    if (lane < nf) lg[lpos + lane] = sx_key(fdis, fv);
+                    lpos += nf;
+                }
             }
             for (int t = 0; t < nf; t++) {
                 const float dis = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fdis), t));
                 const bool cin = hk < ef || dis < sx_dis(top);
-                const bool rin = !lg && dis < rthr;
+                bool rin = !lg && dis < rthr;
                 if (!rin && !cin) continue;
                 const int32_t id = __builtin_amdgcn_readlane(fv, t);
+                if (EXT && rin && mask && mask[id] == 0) {
+                    rin = false;
+                    if (!cin) continue;
+                }
                 const uint64_t key = sx_key(dis, id);
                 if (rin) {
                     sx_sift(rb, k, key, lane);  // res.add_result: heap_replace_top
@@ -700,6 +741,10 @@ __device__ __forceinline__ void hnsw_exact_query(
                 if (hk == ef) top = cb[1];
             }
             __syncthreads();
+            if (EXT && !check_rel && ++l0steps > efSearch) {
+                st_n2 = nvalid == 0 ? 1u : 0u;
+                break;
+            }
         }
     }
     if (stats && lane == 0 && g.entry_point >= 0) {
@@ -864,7 +909,7 @@ __device__ __forceinline__ void hnsw_exact_query(
     }
 }
 
-template <bool LDS_VISITED, bool GH = false>
+template <bool LDS_VISITED, bool GH = false, bool EXT = false>
 __global__ __launch_bounds__(64) void k_hnsw_exact(HNSWDevice g, const float* __restrict__ x,
                                                    int ldx, int64_t n, int k, int efSearch,
                                                    int ef, float* __restrict__ D,
@@ -875,15 +920,180 @@ __global__ __launch_bounds__(64) void k_hnsw_exact(HNSWDevice g, const float* __
                                                    unsigned long long* __restrict__ stats,
                                                    const uint32_t* __restrict__ only,
         const uint32_t* __restrict__ qidx, float* __restrict__ gheap = nullptr,
-        ArrivalLog alog = ArrivalLog{}) {
+        ArrivalLog alog = ArrivalLog{}, bool check_rel = true,
+        const uint8_t* __restrict__ mask = nullptr) {
     // qidx: compact launch over listed queries (input row qidx[b], output
     // row b); else query b, output row b
     const int64_t q = qidx ? (int64_t)qidx[blockIdx.x] : (int64_t)blockIdx.x;
     const int64_t qo = blockIdx.x;
     if (only && only[q] == 0u) return;
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    hnsw_exact_query<LDS_VISITED, GH>(g, x, ldx, k, efSearch, ef, D, I, I32, vis_global, vwords,
-                                      stats, gheap, alog, q, qo, (int64_t)blockIdx.x, sm);
+    hnsw_exact_query<LDS_VISITED, GH, EXT>(g, x, ldx, k, efSearch, ef, D, I, I32, vis_global,
+                                           vwords, stats, gheap, alog, q, qo,
+                                           (int64_t)blockIdx.x, sm, check_rel, mask);
+}
+
+// HNSW::search with bounded_queue false (faiss/impl/HNSW.cpp:975-991 over
+// search_from_candidate_unbounded, :744-848): one wave per query, the greedy
+// descent, visited bitmap and per-hop arrivals of the sequential kernel, and
+// the reference's two std::priority_queues of (distance, id) pairs as binary
+// heaps of sx_key keys — top_candidates a max-heap of at most ef keys,
+// candidates a min-heap (a max-heap of the complemented keys) that takes
+// every admitted arrival, up to ntotal of them.  All pairs are distinct, so
+// the minimum and maximum the reference sees are those of these heaps
+// whatever the layout.  (Once top_candidates is full its maximum never
+// grows, so a candidate strictly beyond it is never expanded and could be
+// dropped if counted for n2; the min-heap here keeps them instead — they sink
+// to its leaves and cost one sift each — so n2 is the heap's own size.)
+// A heap's first nl slots live in the LDS and the rest in the query's global
+// scratch (ub_heap_slots per query), so any ef and any number of pushes are
+// served and a short search never leaves the LDS.
+namespace {
+constexpr int kUbLdsSlots = 1024;  // LDS slots per heap (even: sibling pairs stay together)
+struct UbHeap {
+    uint64_t* lds;   // slots [0, nl)
+    uint64_t* glob;  // slots [nl, ...), indexed by the slot number
+    int nl;
+    __device__ __forceinline__ uint64_t* at(int i) const { return i < nl ? lds + i : glob + i; }
+};
+__host__ __device__ inline int ub_top_cap(int ef, int64_t ntotal) {
+    return (int)(ntotal < (int64_t)ef ? (ntotal < 1 ? 1 : ntotal) : ef);
+}
+// 64-bit slots of global scratch per query: top_candidates, then candidates
+__host__ __device__ inline size_t ub_heap_slots(int ef, int64_t ntotal) {
+    return seq_slots(ub_top_cap(ef, ntotal)) + seq_slots((int)(ntotal < 1 ? 1 : ntotal));
+}
+__host__ __device__ inline int ub_top_lds(int ef, int64_t ntotal) {
+    const size_t s = seq_slots(ub_top_cap(ef, ntotal));
+    return (int)(s < (size_t)kUbLdsSlots ? s : (size_t)kUbLdsSlots);
+}
+// LDS: query | top_candidates' first slots | candidates' first slots | visited
+__host__ __device__ inline size_t ub_lds_bytes(int ld, int ef, int64_t ntotal) {
+    return 4 * (size_t)seq_qpad(ld) + 8 * ((size_t)ub_top_lds(ef, ntotal) + kUbLdsSlots);
+}
+// sx_sift / sx_push over a UbHeap (max-heap of the stored keys)
+__device__ __forceinline__ void ub_sift(const UbHeap& h, int n, uint64_t val, int lane) {
+    int i = 1;
+    for (;;) {
+        const int i1 = 2 * i;
+        if (i1 > n) break;
+        const uint4 pv = *(const uint4*)h.at(i1);
+        const uint64_t k1 = ((uint64_t)pv.y << 32) | pv.x, k2 = ((uint64_t)pv.w << 32) | pv.z;
+        const bool first = i1 + 1 == n + 1 || k1 > k2;
+        const uint64_t kj = first ? k1 : k2;
+        if (val > kj) break;
+        if (lane == 0) *h.at(i) = kj;
+        i = first ? i1 : i1 + 1;
+    }
+    if (lane == 0) *h.at(i) = val;
+}
+__device__ __forceinline__ void ub_push(const UbHeap& h, int n, uint64_t val, int lane) {
+    const int L = 31 - __clz(n);
+    const int j = lane + 1;
+    const bool in = j <= L;
+    const uint64_t a = in ? *h.at(n >> (j & 31)) : 0ull;
+    const unsigned long long gt = __ballot(in && val > a);
+    const int m = __builtin_ctzll(~gt);
+    if (j <= m) *h.at(n >> (j - 1)) = a;
+    if (lane == 0) *h.at(n >> m) = val;
+}
+}  // namespace
+
+template <bool LDS_VISITED>
+__global__ __launch_bounds__(64) void k_hnsw_unbounded(
+        HNSWDevice g, const float* __restrict__ x, int ldx, int64_t n, int k, int ef,
+        float* __restrict__ D, int64_t* __restrict__ I, int32_t* __restrict__ I32,
+        uint32_t* __restrict__ vis_global, int64_t vwords, unsigned long long* __restrict__ stats,
+        const uint32_t* __restrict__ qidx, uint64_t* __restrict__ gheap) {
+    const int64_t q = qidx ? (int64_t)qidx[blockIdx.x] : (int64_t)blockIdx.x;
+    const int64_t qo = blockIdx.x, blk = blockIdx.x;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int qpad = seq_qpad(g.ld);
+    const int lane = threadIdx.x;
+    float* qs = sm;  // [qpad]
+    UbHeap T, C;
+    T.nl = ub_top_lds(ef, g.ntotal);
+    C.nl = kUbLdsSlots;
+    T.lds = (uint64_t*)(sm + qpad);
+    C.lds = T.lds + T.nl;
+    T.glob = gheap + blk * ub_heap_slots(ef, g.ntotal);
+    C.glob = T.glob + seq_slots(ub_top_cap(ef, g.ntotal));
+    uint32_t* vis = LDS_VISITED ? (uint32_t*)(C.lds + C.nl) : vis_global + blk * vwords;
+    for (int j = lane; j < qpad; j += 64) qs[j] = j < g.d ? x[q * ldx + j] : 0.f;
+    for (int64_t w = lane; w < vwords; w += 64) vis[w] = 0u;
+    __syncthreads();
+    uint32_t st_ndis = 0, st_nhops = 0;
+    int ts = 0, cs = 0;  // top_candidates.size(), candidates.size()
+    if (g.entry_point >= 0) {
+        int nearest = g.entry_point;
+        float d_nearest = 0.f;
+        seq_greedy(g, qs, lane, nearest, d_nearest, st_ndis, st_nhops);
+        // the seed enters both queues (:755-758)
+        if (lane == 0) {
+            T.lds[1] = sx_key(d_nearest, nearest);
+            C.lds[1] = ~sx_key(d_nearest, nearest);
+            vis[nearest >> 5] |= 1u << (nearest & 31);
+        }
+        ts = cs = 1;
+        __syncthreads();
+        const int cnt = g.cum_nb[1] - g.cum_nb[0];
+        uint64_t ttop = T.lds[1];
+        while (cs > 0) {
+            const uint64_t ck = ~C.lds[1];
+            if (sx_dis(ck) > sx_dis(ttop)) break;  // distance only (:765)
+            ub_sift(C, cs, *C.at(cs), lane);  // candidates.pop()
+            cs--;
+            int32_t fv;
+            float fdis;
+            const int nf = seq_fresh_rows(g, qs, vis, sx_id(ck), cnt, lane, fv, fdis);
+            st_ndis += (uint32_t)nf;
+            st_nhops += 1;
+            // add_to_heap (:789-799) in arrival order
+            for (int t = 0; t < nf; t++) {
+                const float dis = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fdis), t));
+                if (!(sx_dis(ttop) > dis || ts < ef)) continue;
+                const uint64_t key = sx_key(dis, __builtin_amdgcn_readlane(fv, t));
+                ub_push(C, ++cs, ~key, lane);
+                // push, then pop while over ef: at ef entries the key replaces
+                // the maximum, which it precedes (dis < the maximum's)
+                if (ts < ef)
+                    ub_push(T, ++ts, key, lane);
+                else
+                    ub_sift(T, ts, key, lane);
+                ttop = T.lds[1];
+            }
+            __syncthreads();
+        }
+    }
+    if (stats && lane == 0 && g.entry_point >= 0) {
+        atomicAdd(&stats[0], 1ull);
+        atomicAdd(&stats[1], cs == 0 ? 1ull : 0ull);
+        atomicAdd(&stats[2], (unsigned long long)st_ndis);
+        atomicAdd(&stats[3], (unsigned long long)st_nhops);
+        atomicAdd(&stats[4], (unsigned long long)st_ndis);
+    }
+    // HNSW::search :980-990: top_candidates popped down to k entries, the rest
+    // through res.add_result and heap_reorder — ascending by (dis, id), then
+    // (FLT_MAX, -1) padding
+    while (ts > k) {
+        ub_sift(T, ts, *T.at(ts), lane);
+        ts--;
+    }
+    for (int j = ts + lane; j < k; j += 64) {
+        if (D) D[qo * k + j] = FLT_MAX;
+        if (I) I[qo * k + j] = -1;
+        if (I32) I32[qo * k + j] = -1;
+    }
+    while (ts > 0) {
+        const uint64_t top = T.lds[1];
+        ub_sift(T, ts, *T.at(ts), lane);
+        ts--;
+        if (lane == 0) {
+            if (D) D[qo * k + ts] = sx_dis(top);
+            if (I) I[qo * k + ts] = sx_id(top);
+            if (I32) I32[qo * k + ts] = sx_id(top);
+        }
+    }
 }
 
 // The same sequential search for ef, k <= 64 with both heaps in registers.
@@ -2296,10 +2506,54 @@ static void hnsw_exact_launch(const HNSWDevice& g, const float* x, int ldx, int6
                               unsigned long long* stats, const uint32_t* only,
                               const uint32_t* qidx, hipStream_t s, float* gheap = nullptr,
                               uint64_t* rlog = nullptr, int rcap = 0, void* alog = nullptr,
-                              size_t alog_bytes = 0) {
+                              size_t alog_bytes = 0, const HNSWMode& mode = HNSWMode{}) {
     const int ef = efSearch > k ? efSearch : k;
+    if (!mode.bounded_queue) {
+        // search_from_candidate_unbounded: its own kernel, both queues' tails
+        // in gheap (ub_heap_slots per query)
+        FAISS_THROW_IF_NOT(gheap != nullptr && only == nullptr);
+        const size_t lds_u = ub_lds_bytes(g.ld, ef, g.ntotal);
+        if (lds_u + vwords * 4 <= 64 * 1024)
+            k_hnsw_unbounded<true><<<kgrid(n, 64), dim3(64), lds_u + vwords * 4, s>>>(
+                    g, x, ldx, n, k, ef, D, I, I32, nullptr, vwords, stats, qidx, (uint64_t*)gheap);
+        else
+            k_hnsw_unbounded<false><<<kgrid(n, 64), dim3(64), lds_u, s>>>(
+                    g, x, ldx, n, k, ef, D, I, I32, visited_scratch, vwords, stats, qidx,
+                    (uint64_t*)gheap);
+        HIP_LAUNCH_CHECK();
+        return;
+    }
     const size_t lds_x = seq_lds_bytes(g.ld, ef, k);
     const bool x_lds_vis = lds_x + vwords * 4 <= 64 * 1024;
+    if (!mode.is_default()) {
+        // the stop after efSearch hops and / or a selector: the sequential
+        // kernel's EXT form at every ef and k (never the register kernel)
+        const bool chk = mode.check_relative_distance;
+        if (lds_x > 64 * 1024) {
+            FAISS_THROW_IF_NOT(gheap != nullptr);
+            const size_t lds_g = seq_lds_bytes_gheap(g.ld);
+            if (lds_g + vwords * 4 <= 64 * 1024)
+                k_hnsw_exact<true, true, true><<<kgrid(n, 64), dim3(64), lds_g + vwords * 4, s>>>(
+                        g, x, ldx, n, k, efSearch, ef, D, I, I32, nullptr, vwords, stats, only,
+                        qidx, gheap, ArrivalLog{}, chk, mode.mask);
+            else
+                k_hnsw_exact<false, true, true><<<kgrid(n, 64), dim3(64), lds_g, s>>>(
+                        g, x, ldx, n, k, efSearch, ef, D, I, I32, visited_scratch, vwords, stats,
+                        only, qidx, gheap, ArrivalLog{}, chk, mode.mask);
+        } else {
+            const ArrivalLog al = make_arrival_log(g, k, ef, alog, alog_bytes, s);
+            if (x_lds_vis)
+                k_hnsw_exact<true, false, true><<<kgrid(n, 64), dim3(64), lds_x + vwords * 4, s>>>(
+                        g, x, ldx, n, k, efSearch, ef, D, I, I32, nullptr, vwords, stats, only,
+                        qidx, nullptr, al, chk, mode.mask);
+            else
+                k_hnsw_exact<false, false, true><<<kgrid(n, 64), dim3(64), lds_x, s>>>(
+                        g, x, ldx, n, k, efSearch, ef, D, I, I32, visited_scratch, vwords, stats,
+                        only, qidx, nullptr, al, chk, mode.mask);
+        }
+        HIP_LAUNCH_CHECK();
+        return;
+    }
     if (lds_x > 64 * 1024) {
         // heaps in global scratch; the LDS keeps the query, the hop's fresh
         // neighbours and (when it fits) the visited bitmap
@@ -2413,15 +2667,21 @@ void hnsw_flag_compact(const uint32_t* flags, int64_t n, uint32_t* idx, uint32_t
 void hnsw_exact_listed(const HNSWDevice& g, const float* x, int ldx, const uint32_t* qidx,
                        int64_t nf, int k, int efSearch, float* D, int32_t* I32,
                        uint32_t* visited_scratch, int64_t vwords, unsigned long long* stats,
-                       hipStream_t s, void* arrival_log, size_t arrival_log_bytes) {
+                       hipStream_t s, void* arrival_log, size_t arrival_log_bytes,
+                       const HNSWMode& mode) {
     if (nf <= 0) return;
+    // (no heap scratch here: the listed form serves the split of the default
+    // mode, whose callers keep other modes away)
+    FAISS_THROW_IF_NOT(mode.bounded_queue);
     hnsw_exact_launch(g, x, ldx, nf, k, efSearch, D, nullptr, I32, visited_scratch, vwords,
                       stats, nullptr, qidx, s, nullptr, nullptr, 0, arrival_log,
-                      arrival_log_bytes);
+                      arrival_log_bytes, mode);
 }
 
-size_t hnsw_heap_scratch_words(int k, int efSearch, int ld) {
+size_t hnsw_heap_scratch_words(int k, int efSearch, int ld, const HNSWMode& mode,
+                               int64_t ntotal) {
     const int ef = efSearch > k ? efSearch : k;
+    if (!mode.bounded_queue) return 2 * ub_heap_slots(ef, ntotal);
     return seq_lds_bytes(ld, ef, k) > 64 * 1024 ? seq_heap_bytes(ef, k) / 4 : 0;
 }
 // FAISS_AMD_HNSW_WIDE_GVIS=1: the wide kernel's visited bitmap in global
@@ -2430,17 +2690,21 @@ static bool wide_global_visited() {
     const char* e = getenv("FAISS_AMD_HNSW_WIDE_GVIS");
     return e && !strcmp(e, "1");
 }
-bool hnsw_visited_scratch_needed(int ld, int k, int efSearch, int64_t vwords) {
+bool hnsw_visited_scratch_needed(int ld, int k, int efSearch, int64_t vwords,
+                                 const HNSWMode& mode) {
     // mirrors the LDS choices of the three kernels: any query may reach the
     // sequential kernel (ties of the batched one), the register kernel keeps
     // its own head (exact_reg_head) before the bitmap
     constexpr size_t kL = 64 * 1024;
     const int ef = efSearch > k ? efSearch : k;
     const size_t vb = 4 * (size_t)std::max<int64_t>(vwords, 0);
+    // (k_hnsw_unbounded: vwords = ceil(ntotal / 32) bounds ntotal from above)
+    if (!mode.bounded_queue) return ub_lds_bytes(ld, ef, 32 * std::max<int64_t>(vwords, 1)) + vb > kL;
     const size_t lds_q = sizeof(float) * (size_t)ld;
     const size_t lds_x = seq_lds_bytes(ld, ef, k);
     const size_t lds_xg = lds_x > kL ? seq_lds_bytes_gheap(ld) : lds_x;
     bool need = lds_xg + vb > kL;
+    if (!mode.is_default()) return need;  // the sequential kernel alone
     if (ef <= 64 && k <= 64 && lds_x <= kL) {
         HNSWDevice g{};
         g.ld = ld;
@@ -2455,19 +2719,21 @@ bool hnsw_visited_scratch_needed(int ld, int k, int efSearch, int64_t vwords) {
     }
     return need;
 }
-bool hnsw_register_eligible(int k, int efSearch) {
+bool hnsw_register_eligible(int k, int efSearch, const HNSWMode& mode) {
     const int ef = efSearch > k ? efSearch : k;
-    return ef <= 64 && k <= 64;
+    return mode.is_default() && ef <= 64 && k <= 64;
 }
 // the wide kernel (k_hnsw_wide): 128 < ef <= kHnswWideMaxEf (its sorted set
 // in the LDS, 8 B per entry); FAISS_AMD_HNSW_WIDE=0: the sequential kernel
-bool hnsw_uses_wide(int k, int efSearch) {
+bool hnsw_uses_wide(int k, int efSearch, const HNSWMode& mode) {
+    if (!mode.is_default()) return false;
     const int ef = efSearch > k ? efSearch : k;
     const char* wenv = getenv("FAISS_AMD_HNSW_WIDE");
     if (wenv && !strcmp(wenv, "0")) return false;
     return ef > 128 && ef <= kHnswWideMaxEf;
 }
-bool hnsw_uses_batched(int k, int efSearch) {
+bool hnsw_uses_batched(int k, int efSearch, const HNSWMode& mode) {
+    if (!mode.is_default()) return false;
     const int ef = efSearch > k ? efSearch : k;
     const char* menv = getenv("FAISS_AMD_HNSW");
     const bool prefer_batched = menv && !strcmp(menv, "batched");
@@ -2479,7 +2745,7 @@ void hnsw_search(const HNSWDevice& g, const float* x, int ldx, int64_t n, int k,
                  int64_t visited_words_per_query, unsigned long long* stats, uint32_t* flags,
                  hipStream_t s, KernelTimes* kt, bool defer, float* heap_scratch,
                  uint64_t* replay_log, int64_t replay_cap, void* arrival_log,
-                 size_t arrival_log_bytes) {
+                 size_t arrival_log_bytes, const HNSWMode& mode) {
     if (n <= 0) return;
     FAISS_THROW_IF_NOT_FMT(k >= 1, "k = %d must be >= 1", k);
     const int ef = efSearch > k ? efSearch : k;
@@ -2488,12 +2754,12 @@ void hnsw_search(const HNSWDevice& g, const float* x, int ldx, int64_t n, int k,
     const size_t lds_q = sizeof(float) * g.ld;
     // FAISS_AMD_HNSW=batched: the batched kernel (+ sequential re-runs of
     // tied queries) also where the register kernel serves every query
-    const bool batched = hnsw_uses_batched(k, efSearch);
+    const bool batched = hnsw_uses_batched(k, efSearch, mode);
     // sequential kernel: query | ef heap | k heap | 64 fresh | 8 scalars | visited
     // (heaps in global scratch when they do not fit)
     // the batched kernel: query | visited in the LDS when both fit
     const bool lds_vis = lds_q + (size_t)vwords * 4 <= 64 * 1024;
-    if (hnsw_visited_scratch_needed(g.ld, k, efSearch, vwords)) {
+    if (hnsw_visited_scratch_needed(g.ld, k, efSearch, vwords, mode)) {
         FAISS_THROW_IF_NOT(visited_scratch != nullptr);
         HIP_CHECK(hipMemsetAsync(visited_scratch, 0, sizeof(uint32_t) * vwords * n, s));
     }
@@ -2502,7 +2768,7 @@ void hnsw_search(const HNSWDevice& g, const float* x, int ldx, int64_t n, int k,
         hnsw_exact_launch(g, x, ldx, n, k, efSearch, D, I, I32, visited_scratch, vwords, stats,
                           only, nullptr, s, heap_scratch, replay_cap > 0 ? replay_log : nullptr,
                           (int)std::min<int64_t>(replay_cap, kHnswReplayCap), arrival_log,
-                          arrival_log_bytes);
+                          arrival_log_bytes, mode);
     };
     // FAISS_AMD_HNSW_EXACT=1: every query through the sequential kernel (tests)
     const char* xenv = getenv("FAISS_AMD_HNSW_EXACT");

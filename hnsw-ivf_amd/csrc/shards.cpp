@@ -384,7 +384,11 @@ Index* clone_to_device(const Index* src, int device) {
     idx->device = device;
     if (auto* h = dynamic_cast<IndexHNSW*>(idx)) {
         if (h->storage) h->storage->device = device;
-        h->hnsw.efSearch = dynamic_cast<const IndexHNSW*>(src)->hnsw.efSearch;
+        // (search-time fields the index file does not carry)
+        const HNSW& sh = dynamic_cast<const IndexHNSW*>(src)->hnsw;
+        h->hnsw.efSearch = sh.efSearch;
+        h->hnsw.check_relative_distance = sh.check_relative_distance;
+        h->hnsw.search_bounded_queue = sh.search_bounded_queue;
     }
     return idx;
 }

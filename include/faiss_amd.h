@@ -90,6 +90,8 @@ struct SearchParameters {  // faiss/Index.h:63-70
 };
 struct SearchParametersHNSW : SearchParameters {  // faiss/impl/HNSW.h:46-52
     int efSearch = 16;
+    bool check_relative_distance = true;
+    bool bounded_queue = true;
 };
 struct SearchParametersIVF : SearchParameters {  // faiss/IndexIVF.h:77-85
     size_t nprobe = 1;
@@ -280,6 +282,10 @@ struct IndexFlat : Index {
 
     const float* device_vectors() const;  // [ntotal][ld]
     const float* device_norms() const;
+    // the row numbers 0 .. ntotal - 1 (int64) on the device, built on first
+    // use: the id table IDSelector::mark_device reads for a selector over the
+    // rows (also the nodes of an IndexHNSW over this storage)
+    const idx_t* device_row_ids(hipStream_t stream) const;
     // assign_device that also leaves the batch's query image (kernels.h
     // query_prep: bf16 fragments, then |x|^2 at byte query_image_bytes(n, d))
     // in the caller's buffer `qimg` (query_image_bytes(n, d) + 4 n bytes), on
@@ -381,8 +387,9 @@ struct IndexHNSW : Index {
     // overlap them with its own work (IndexIVF::search_device): split_begin
     // queues the batched search of n queries (the flagged ones keep the
     // batched result) and a read-back of the flagged count, and returns false
-    // when this form is not offered (visited bitmaps beyond LDS, ef > 128 or
-    // k > 64: the caller then uses assign_device).  split_finish waits for the
+    // when this form is not offered (visited bitmaps beyond LDS, ef > 128,
+    // k > 64, or a search mode other than the default or a selector, see
+    // search_mode: the caller then uses assign_device).  split_finish waits for the
     // count, queues the reference-exact sequential search of the flagged
     // queries on a side stream into compact rows, and returns them; `done` is
     // recorded after it (the caller waits on it before reading D / I).
@@ -408,6 +415,23 @@ struct IndexHNSW : Index {
         }
     };
 
+    // What a search with `params` runs (faiss/impl/HNSW.cpp:619-622, :954-955,
+    // :967): with a SearchParametersHNSW every value is the object's own, the
+    // fields left at their defaults included, and the index-level values act
+    // only when params is null; sel comes from the params alone.  Params of
+    // another type throw "params type invalid".
+    struct SearchMode {
+        int efSearch = 16;
+        bool check_relative_distance = true;
+        bool bounded_queue = true;
+        const IDSelector* sel = nullptr;
+        // the mode the register, batched and wide kernels serve (bounded_queue
+        // false reads neither check_relative_distance nor sel, as the
+        // reference's search_from_candidate_unbounded does not)
+        bool is_default() const { return bounded_queue && check_relative_distance && !sel; }
+    };
+    SearchMode search_mode(const SearchParameters* params) const;
+
    private:
     template <class OutIdx>
     void hnsw_device(idx_t n, const float* x, int ldx, int k, float* distances, OutIdx* labels,
@@ -416,6 +440,10 @@ struct IndexHNSW : Index {
     mutable DeviceBuffer d_levels_, d_offsets_, d_neighbors_, d_cum_, d_nb0_, s_visited_, d_stats_,
             s_flags_, s_fidx_, s_fcnt_, s_fD_, s_fI_, s_heaps_, s_rlog_, d_q8_, d_q8p_, d_q8q1_,
             s_alog_;  // the sequential kernel's arrival-log pool
+    // (s_rlog_: the register kernel's replay logs, or, in a search with a
+    // selector, which that kernel never serves, the selector's membership
+    // bytes over the nodes.  No member is added for the selector, so the
+    // object's layout stays the one earlier builds of callers were given.)
     mutable bool q8_ = false;  // the int8 level-0 row image is built
     mutable uint32_t* h_fcnt_ = nullptr;  // pinned read-back of the flagged count
     mutable hipEvent_t ev_split_ = nullptr, ev_exact_ = nullptr;

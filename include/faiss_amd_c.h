@@ -176,6 +176,35 @@ void faiss_amd_IndexIVF_set_parallel_mode(FaissIndexIVF*, int);
 void faiss_amd_SearchParametersIVF_set_quantizer_efSearch(
         FaissSearchParametersIVF*,
         int);
+/* extension: every field of the quantizer's SearchParametersHNSW for this
+ * call (faiss/impl/HNSW.h:46-52).  As in the reference the object replaces
+ * the index-level values altogether: check_relative_distance = 0 stops after
+ * efSearch level-0 hops, bounded_queue = 0 runs
+ * search_from_candidate_unbounded. */
+void faiss_amd_SearchParametersIVF_set_quantizer_hnsw(
+        FaissSearchParametersIVF*,
+        int efSearch,
+        int check_relative_distance,
+        int bounded_queue);
+/* extension: SearchParametersHNSW (the reference C API has none), for
+ * faiss_Index_search_with_params on an IndexHNSW and
+ * faiss_amd_IndexHNSW_search_stats.  sel may be NULL and is not owned; it
+ * filters the results, not the traversal, and is ignored with
+ * bounded_queue = 0 (as in the reference).  Free with
+ * faiss_amd_SearchParametersHNSW_free. */
+int faiss_amd_SearchParametersHNSW_new(
+        FaissSearchParameters** p_sp,
+        int efSearch,
+        int check_relative_distance,
+        int bounded_queue,
+        FaissIDSelector* sel);
+void faiss_amd_SearchParametersHNSW_free(FaissSearchParameters*);
+/* extension: SearchParametersIVF::quantizer_params = a parameter object of
+ * this API (e.g. one with a selector over list numbers); not owned, NULL
+ * clears it */
+void faiss_amd_SearchParametersIVF_set_quantizer_params(
+        FaissSearchParametersIVF*,
+        FaissSearchParameters* quantizer_params);
 
 /* ---------------- IndexFlat (c_api/IndexFlat_c.h) ---------------- */
 /* IndexFlat_c.h:28-31 */
@@ -446,6 +475,12 @@ int faiss_amd_IndexHNSWFlat_new_with(
         FaissMetricType metric);
 int faiss_amd_IndexHNSW_efSearch(const FaissIndexHNSW*);
 void faiss_amd_IndexHNSW_set_efSearch(FaissIndexHNSW*, int);
+/* HNSW::check_relative_distance / search_bounded_queue (faiss/impl/HNSW.h):
+ * the search mode when no SearchParametersHNSW is passed */
+int faiss_amd_IndexHNSW_check_relative_distance(const FaissIndexHNSW*);
+void faiss_amd_IndexHNSW_set_check_relative_distance(FaissIndexHNSW*, int);
+int faiss_amd_IndexHNSW_search_bounded_queue(const FaissIndexHNSW*);
+void faiss_amd_IndexHNSW_set_search_bounded_queue(FaissIndexHNSW*, int);
 int faiss_amd_IndexHNSW_efConstruction(const FaissIndexHNSW*);
 void faiss_amd_IndexHNSW_set_efConstruction(FaissIndexHNSW*, int);
 /* the flat storage index of an IndexHNSW (owned by it) */
@@ -632,6 +667,17 @@ int faiss_amd_Index_search_device(
         idx_t n,
         const float* x_dev,
         idx_t k,
+        float* distances_dev,
+        idx_t* labels_dev,
+        void* stream);
+/* the same with search parameters (NULL: none), e.g. a SearchParametersHNSW
+ * on an IndexHNSW or a SearchParametersIVF on an IVF index */
+int faiss_amd_Index_search_device_with_params(
+        const FaissIndex* index,
+        idx_t n,
+        const float* x_dev,
+        idx_t k,
+        const FaissSearchParameters* params,
         float* distances_dev,
         idx_t* labels_dev,
         void* stream);
