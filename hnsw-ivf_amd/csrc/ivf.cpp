@@ -1510,10 +1510,22 @@ void ProductQuantizer::set_derived_values() {
     centroids.resize(d * ksub);
 }
 
+namespace {
+// before ProductQuantizer sizes its 2^nbits centroids
+size_t checked_pq_nbits(size_t nbits) {
+    FAISS_THROW_IF_NOT_FMT(nbits >= 4 && nbits <= 8,
+                           "IndexIVFPQ: nbits = %zu is not supported on this path "
+                           "(nbits 4, 5, 6, 7 and 8 are)",
+                           nbits);
+    return nbits;
+}
+}  // namespace
+
 IndexIVFPQ::IndexIVFPQ(Index* q, size_t d_, size_t nl, size_t M, size_t nbits, MetricType metric)
-        : IndexIVF(q, d_, nl, 0, metric), pq(d_, M, nbits) {
-    FAISS_THROW_IF_NOT_MSG(nbits == 8, "only nbits = 8 is supported on this path");
-    code_size = M;  // (M * nbits + 7) / 8
+        : IndexIVF(q, d_, nl, 0, metric), pq(d_, M, checked_pq_nbits(nbits)) {
+    // PQEncoderGeneric's little-endian bit stream (faiss/impl/ProductQuantizer-inl.h:
+    // 10-97): index m in bits [m * nbits, (m + 1) * nbits), top bits of the last byte 0
+    code_size = (M * nbits + 7) / 8;
     invlists = std::make_unique<ArrayInvertedLists>(nlist, code_size);
     by_residual = true;
     is_trained = false;
@@ -1566,7 +1578,9 @@ void IndexIVFPQ::encode_vectors(idx_t n, const float* x, const idx_t* list_nos,
     DevGuard dg(device);
     hipStream_t s = stream();
     const int ldx = ld();
-    const int cs = device_code_stride();
+    // k_pq_encode writes one byte per index at a stride of roundup(M, 4)
+    // (nbits = 8: the device code stride); narrower indexes are packed below
+    const int cs = (int)roundup(pq.M, 4);
     std::vector<int32_t> a32(n);
     for (idx_t i = 0; i < n; i++) a32[i] = (int32_t)std::max<idx_t>(list_nos[i], 0);
     std::vector<float> cent((size_t)nlist * ldx, 0.f);
@@ -1592,8 +1606,25 @@ void IndexIVFPQ::encode_vectors(idx_t n, const float* x, const idx_t* list_nos,
     std::vector<uint8_t> hc((size_t)n * cs);
     HIP_CHECK(hipMemcpyAsync(hc.data(), bo.ptr, hc.size(), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    for (idx_t i = 0; i < n; i++) memcpy(codes + (size_t)i * code_size, hc.data() + (size_t)i * cs,
-                                         code_size);
+    if (pq.nbits == 8) {
+        for (idx_t i = 0; i < n; i++)
+            memcpy(codes + (size_t)i * code_size, hc.data() + (size_t)i * cs, code_size);
+        return;
+    }
+    // PQEncoderGeneric (faiss/impl/ProductQuantizer-inl.h:10-55): little-endian
+    // bit stream, the last byte's top bits zero
+    const int nb = (int)pq.nbits;
+    for (idx_t i = 0; i < n; i++) {
+        uint8_t* out = codes + (size_t)i * code_size;
+        const uint8_t* in = hc.data() + (size_t)i * cs;
+        memset(out, 0, code_size);
+        for (size_t m = 0; m < pq.M; m++) {
+            const size_t o = m * nb;
+            const uint32_t v = (uint32_t)in[m] << (o & 7);
+            out[o >> 3] |= (uint8_t)v;
+            if ((o & 7) + nb > 8) out[(o >> 3) + 1] |= (uint8_t)(v >> 8);
+        }
+    }
 }
 
 const void* IndexIVFPQ::stream_image(size_t* row_bytes) const {
@@ -1615,9 +1646,10 @@ void IndexIVFPQ::upload_extra() const {
     HIP_CHECK(hipMemcpyAsync(d_cent_.ptr, cent.data(), sizeof(float) * cent.size(),
                              hipMemcpyHostToDevice, s));
     if (by_residual && arena_rows_ > 0)
-        kern::ivfpq_terms(d_codes_.as<uint8_t>(), d_row_list_.as<uint32_t>(), arena_rows_,
-                          d_cent_.as<float>(), ldc, d_pq_.as<float>(), (int)pq.M, (int)pq.ksub,
-                          (int)pq.dsub, d_terms_.as<float>(), s);
+        kern::ivfpq_terms(d_codes_.as<uint8_t>(), device_code_stride(), (int)pq.nbits,
+                          d_row_list_.as<uint32_t>(), arena_rows_, d_cent_.as<float>(), ldc,
+                          d_pq_.as<float>(), (int)pq.M, (int)pq.ksub, (int)pq.dsub,
+                          d_terms_.as<float>(), s);
     // list-centric MFMA scan: decode table, row / list norms (any k, nprobe)
     pq_mfma_ready_ = false;
     if (by_residual && metric_type == METRIC_L2 && pq.ksub == 256 &&
@@ -1803,6 +1835,85 @@ void IndexIVFPQ::search_preassigned_device(idx_t n, const float* x, int ldx, idx
         }
         return;
     }
+    // packed codes (nbits < 8): the list-centric scan with the tables in LDS
+    // (kernels_pq_lut.hip; L2 and IP, both tables, by residual or not).  It is
+    // the general scan's answer; k past IVFPQ_LUT_KMAX, tables past its LDS
+    // budget, store_pairs and duplicate probes take the general scan.
+    if (!force_exact && !store_pairs && !dup_probes_ && pq.nbits < 8 &&
+        kern::ivfpq_lut_eligible((int)pq.M, (int)pq.nbits, device_code_stride(), ldx, (int)k)) {
+        std::lock_guard<std::recursive_mutex> g(mu_);
+        const int QT = kern::IVFPQ_LUT_QT;
+        // queries per pass: the candidate buffers (24 KB per query) stay under ~400 MB
+        const idx_t qc = std::min<idx_t>(n, 16384);
+        s_lut_.reserve(sizeof(uint32_t) * kern::ivfpq_lut_scratch_words(qc));
+        s_cur_.reserve(sizeof(uint32_t) * std::max<idx_t>(qc * np, 1));
+        s_boff_.reserve(sizeof(uint32_t) * (nlist + 1));
+        s_ioff_.reserve(sizeof(uint32_t) * (nlist + 1));
+        s_ent_.reserve(sizeof(uint32_t) * qc * np);
+        const int64_t mi = kern::ivf_max_items(qc, np, (int)nlist, QT);
+        s_idesc_.reserve(sizeof(kern::ItemDesc) * mi);
+        s_ient_.reserve(sizeof(uint32_t) * mi * QT);
+        s_ictr_.reserve(16 + 4 * 3 * 64);
+        kern::ExactScanArgs a;
+        exact_args(&a);
+        a.ldx = ldx;
+        a.d = d;
+        a.np = np;
+        a.k = (int)k;
+        a.l2 = metric_type == METRIC_L2;
+        a.list_off = d_list_off_.as<uint32_t>();
+        a.list_len = d_list_len_.as<uint32_t>();
+        a.nlist = (int)nlist;
+        a.sel = sel;
+        a.ids = d_ids_.as<int64_t>();
+        for (idx_t q0 = 0; q0 < n; q0 += qc) {
+            a.n = std::min(qc, n - q0);
+            a.x = x + q0 * ldx;
+            a.assign = assign + q0 * np;
+            a.cdis = centroid_dis ? centroid_dis + q0 * np : nullptr;
+            a.lim = lim ? lim + q0 * np : nullptr;
+            a.qdone = qdone_ ? qdone_ + q0 : nullptr;
+            uint32_t* counts_next = nullptr;
+            uint32_t* counts = bucket_counts(s, &counts_next);
+            kern::IVFBuckets b{counts, s_boff_.as<uint32_t>(), s_ioff_.as<uint32_t>(),
+                               s_cur_.as<uint32_t>(), s_ent_.as<uint32_t>()};
+            b.item_ctr = s_ictr_.as<uint32_t>();
+            b.scan_tmp = s_ictr_.as<uint32_t>() + 4;
+            b.counts_next = counts_next;
+            b.lim = a.lim;
+            b.sel = sel;
+            b.perm = d_list_perm_.as<uint32_t>();
+            b.item_desc = s_idesc_.as<kern::ItemDesc>();
+            b.item_entries = s_ient_.as<uint32_t>();
+            {
+                ScopedKernelTimer tb(&ktimes, "ivf_bucket", 0.0, s);
+                kern::ivf_bucket(a.assign, a.n, np, d_list_len_.as<uint32_t>(),
+                                 d_list_off_.as<uint32_t>(), (int)nlist, QT, b, s);
+            }
+            flip_counts();
+            ScopedKernelTimer tm(&ktimes, "ivfpq_lut", 0.0, s);
+            kern::ivfpq_lut_search(a, b, kern::ivf_max_items(a.n, np, (int)nlist, QT), QT,
+                                   s_lut_.as<uint32_t>(), distances + q0 * k, labels + q0 * k, s);
+            if (getenv("FAISS_AMD_IVF_STATS")) {  // the per-query candidate counters
+                std::vector<uint32_t> cnt(a.n);
+                HIP_CHECK(hipMemcpyAsync(cnt.data(), s_lut_.as<uint32_t>() + a.n,
+                                         sizeof(uint32_t) * a.n, hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+                uint64_t tot = 0;
+                uint32_t mx = 0, over = 0;
+                for (uint32_t c : cnt) {
+                    tot += c;
+                    mx = std::max(mx, c);
+                    over += c > (uint32_t)kern::IVFPQ_LUT_CAP;
+                }
+                fprintf(stderr,
+                        "[faiss_amd] ivfpq lut scan: nq=%lld candidates/q=%.2f max=%u "
+                        "overflow queries=%u (buffer %d)\n",
+                        (long long)a.n, tot / (double)a.n, mx, over, kern::IVFPQ_LUT_CAP);
+            }
+        }
+        return;
+    }
     exact_scan_device(n, x, ldx, k, np, assign, centroid_dis, distances, labels, s, lim, sel,
                       store_pairs);
 }
@@ -1820,6 +1931,7 @@ void IndexIVFPQ::exact_args(void* p) const {
     auto& a = *(kern::ExactScanArgs*)p;
     a.pq.M = (int)pq.M;
     a.pq.dsub = (int)pq.dsub;
+    a.pq.nbits = (int)pq.nbits;
     a.pq.by_residual = by_residual ? 1 : 0;
     a.pq.table1 = (metric_type == METRIC_L2 && by_residual && use_precomputed_table == 1) ? 1 : 0;
     a.pq.pq_cent = d_pq_.as<float>();

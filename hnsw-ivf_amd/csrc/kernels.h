@@ -229,9 +229,10 @@ void device_stamp(unsigned long long* out, hipStream_t s);
 // IVF-PQ tables of the exact scan (QueryTables semantics)
 struct ExactPQ {
     int M = 0, dsub = 0;
+    int nbits = 8;                   // 4..8; < 8: packed codes (pq_ref.h pq_index)
     int by_residual = 1;
     int table1 = 0;                  // use_precomputed_table == 1 (L2 by residual)
-    const float* pq_cent = nullptr;  // [M][256][dsub]
+    const float* pq_cent = nullptr;  // [M][1 << nbits][dsub]
     const float* cent = nullptr;     // coarse centroids [nlist][ldcent] fp32
     int ldcent = 0;
     const uint8_t* codes = nullptr;  // arena codes
@@ -281,6 +282,17 @@ void ivf_exact_search(const ExactScanArgs& a, uint32_t* eoff, uint32_t* total, u
 // a.x / a.assign / a.cdis / a.sel / a.ids / a.row_list / a.store_pairs used)
 void ivfpq_range_exact(const ExactScanArgs& a, float radius, uint32_t* counts,
                        const uint64_t* offsets, float* outD, int64_t* outI, hipStream_t s);
+// IVF-PQ list scan with the tables in LDS, packed codes of 4..7 bits
+// (kernels_pq_lut.hip): the general scan's answer for k <= IVFPQ_LUT_KMAX.
+// Work items of IVFPQ_LUT_QT queries from ivf_bucket (b.item_off / item_desc /
+// item_entries; a.lim / a.sel as the buckets'); scratch: ivfpq_lut_scratch_words(n)
+// 32-bit words (per query a bound, a counter and IVFPQ_LUT_CAP candidates).
+// Not for store_pairs or duplicate probes.
+constexpr int IVFPQ_LUT_QT = 64, IVFPQ_LUT_KMAX = 64, IVFPQ_LUT_CAP = 2048;
+bool ivfpq_lut_eligible(int M, int nbits, int code_stride, int ldx, int k);
+size_t ivfpq_lut_scratch_words(int64_t n);
+void ivfpq_lut_search(const ExactScanArgs& a, const IVFBuckets& b, int64_t max_items, int QT,
+                      uint32_t* scratch, float* D, int64_t* I, hipStream_t s);
 // exact top-k (reference heap semantics, label = col0 + column) of dense rows;
 // k > kMaxKExact runs with global scratch (required then)
 template <class OutIdx>
@@ -373,13 +385,15 @@ void split_bf16_stream(const float* codes, int64_t rows, int d, int ldc, int DB,
                        const float* ynorm, const uint32_t* row_list, void* out, hipStream_t s,
                        int fold = 0);
 // ---------------- IVF-PQ ----------------
-// term[v] = sum_m (||c_{m,code}||^2 + 2 <yC_m, c_{m,code}>) for every arena row
-void ivfpq_terms(const uint8_t* codes, const uint32_t* row_list, int64_t nrows,
-                 const float* centroids, int ldcent, const float* pq_centroids, int M, int ksub,
-                 int dsub, float* terms, hipStream_t s);
+// term[v] = sum_m (||c_{m,code}||^2 + 2 <yC_m, c_{m,code}>) for every arena row;
+// codes: code_stride bytes per row, nbits < 8 packed (pq_ref.h pq_index)
+void ivfpq_terms(const uint8_t* codes, int code_stride, int nbits, const uint32_t* row_list,
+                 int64_t nrows, const float* centroids, int ldcent, const float* pq_centroids,
+                 int M, int ksub, int dsub, float* terms, hipStream_t s);
 
 // PQ encoding: codes[i][m] = argmin_j ||r_im - c_mj||^2 (first minimum)
-// residual r = x - centroid[assign[i]] when centroids != null.
+// residual r = x - centroid[assign[i]] when centroids != null.  One byte per
+// index at a stride of roundup(M, 4), whatever ksub (the caller packs).
 void pq_encode(const float* x, int ldx, int64_t n, const int32_t* assign,
                const float* centroids, int ldcent, const float* pq_centroids, int M, int ksub,
                int dsub, uint8_t* codes, hipStream_t s);

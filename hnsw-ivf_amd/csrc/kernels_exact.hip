@@ -32,6 +32,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "pq_ref.h"
+#include "pq_tables.h"
 #include "ref_arith.h"
 #include "wave_select.h"
 
@@ -95,62 +96,10 @@ __global__ __launch_bounds__(64) void k_ex_flat(const float* __restrict__ x, int
 }
 
 // ---------------------------------------------------------------- PQ
-// The (query, probe) table in LDS with the reference arithmetic (QueryTables,
-// faiss/IndexIVFPQ.cpp:545-700): lut [M * 256] | xs [ldx] | rs [ldx] | dis0.
-// 256 threads; returns dis0 (all threads, after the barrier).
-template <bool L2>
-__device__ __forceinline__ float ex_pq_tables(const float* __restrict__ xq, int ldx, int d,
-                                              int32_t key, float cd, const ExactPQ& pq,
-                                              float* lut) {
-    const int M = pq.M, dsub = pq.dsub;
-    float* xs = lut + M * 256;
-    float* rs = xs + ldx;
-    float* sd0 = rs + ldx;
-    const int tid = threadIdx.x;
-    const float* yc = pq.cent + (int64_t)key * pq.ldcent;
-    for (int i = tid; i < ldx; i += 256) {
-        const float v = xq[i];
-        xs[i] = v;
-        rs[i] = i < d ? v - yc[i] : 0.f;  // Index::compute_residual (faiss/Index.cpp:107-112)
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float d0 = 0.f;
-        if (pq.by_residual) {
-            if (!L2)  // precompute_list_tables_IP: <x, y_C> (faiss/IndexIVFPQ.cpp:612-628)
-                d0 = ref_dist_s<false>(xs, yc, d);
-            else if (pq.table1)
-                d0 = cd;
-        }
-        *sd0 = d0;
-    }
-    for (int ent = tid; ent < M * 256; ent += 256) {
-        const int m = ent >> 8;
-        const float* c = pq.pq_cent + (int64_t)ent * dsub;
-        float v;
-        if (!L2 || !pq.by_residual) {
-            // IP table of x (init_query_IP) / distance table of x (not by residual)
-            v = ny_entry<L2>(xs + m * dsub, c, dsub);
-        } else if (pq.table1) {
-            const float P = fmaf(2.f, ny_entry<false>(yc + m * dsub, c, dsub),
-                                 ref_dist_s<false>(c, c, dsub));
-            v = fmaf(-2.f, ny_entry<false>(xs + m * dsub, c, dsub), P);
-        } else {
-            v = ny_entry<true>(rs + m * dsub, c, dsub);
-        }
-        lut[ent] = v;
-    }
-    __syncthreads();
-    return *sd0;
-}
-
-__device__ __forceinline__ float ex_pq_code(const float* lut, int M, const uint8_t* code) {
-    return pq_code_sum(M, [&](int m) { return lut[m * 256 + code[m]]; });
-}
-
+// (the (query, probe) table and the code sum: pq_tables.h)
 // one 256-thread workgroup per (query, probe): tables, then a thread per row
 // sums its code in the distance_four_codes order.
-template <bool L2>
+template <bool L2, int NB>
 __global__ __launch_bounds__(256) void k_ex_pq(const float* __restrict__ x, int ldx, int d, int np,
                                                const int32_t* __restrict__ assign,
                                                const float* __restrict__ cdis,
@@ -169,14 +118,14 @@ __global__ __launch_bounds__(256) void k_ex_pq(const float* __restrict__ x, int 
     const uint32_t len = lim ? lim[e] : list_len[key];
     if (len == 0) return;
     const float d0 =
-            ex_pq_tables<L2>(x + q * ldx, ldx, d, key, cdis ? cdis[e] : 0.f, pq, lut);
+            ex_pq_tables<L2, NB>(x + q * ldx, ldx, d, key, cdis ? cdis[e] : 0.f, pq, lut);
     const uint32_t off = list_off[key];
     const int64_t base = q * cap + eoff[e];
     for (uint32_t r = threadIdx.x; r < len; r += 256) {
         const uint32_t row = off + r;
         uint32_t k = EX_SKIP;
         if (!sel || sel[row])
-            k = ex_key(d0 + ex_pq_code(lut, pq.M, pq.codes + (int64_t)row * pq.cs), L2);
+            k = ex_key(d0 + ex_pq_code<NB>(lut, pq, pq.codes + (int64_t)row * pq.cs), L2);
         okeys[base + r] = k;
         orows[base + r] = row;
     }
@@ -186,7 +135,7 @@ __global__ __launch_bounds__(256) void k_ex_pq(const float* __restrict__ x, int 
 // scan_codes_range with RangeSearchResults :780-799: kept when
 // C::cmp(radius, dis)).  Workgroup per (query, probe); pass 1 counts, pass 2
 // writes the hits in row order at offsets[qp] (ordered block prefix).
-template <bool L2, bool FILL>
+template <bool L2, bool FILL, int NB>
 __global__ __launch_bounds__(256) void k_ex_pq_range(
         const float* __restrict__ x, int ldx, int d, int np, const int32_t* __restrict__ assign,
         const float* __restrict__ cdis, const uint32_t* __restrict__ list_off,
@@ -205,14 +154,14 @@ __global__ __launch_bounds__(256) void k_ex_pq_range(
     if (key >= 0 && key < nlist && list_len[key] > 0) {
         const uint32_t len = list_len[key], off = list_off[key];
         const float d0 =
-                ex_pq_tables<L2>(x + q * ldx, ldx, d, key, cdis ? cdis[e] : 0.f, pq, lut);
+                ex_pq_tables<L2, NB>(x + q * ldx, ldx, d, key, cdis ? cdis[e] : 0.f, pq, lut);
         const uint64_t base = FILL ? offsets[e] : 0;
         for (uint32_t r0 = 0; r0 < len; r0 += 256) {
             const uint32_t r = r0 + tid;
             bool hit = false;
             float dis = 0.f;
             if (r < len && (!sel || sel[off + r])) {
-                dis = d0 + ex_pq_code(lut, pq.M, pq.codes + (int64_t)(off + r) * pq.cs);
+                dis = d0 + ex_pq_code<NB>(lut, pq, pq.codes + (int64_t)(off + r) * pq.cs);
                 hit = L2 ? dis < radius : dis > radius;
             }
             const uint64_t bm = __ballot(hit);
@@ -442,6 +391,17 @@ size_t select_lds(int k) {
     return KS * (sizeof(int64_t) + sizeof(uint32_t)) + (size_t)k * sizeof(int64_t);
 }
 
+// dynamic LDS of k_ex_pq / k_ex_pq_range (ex_pq_tables' layout)
+size_t ex_pq_lds(const ExactScanArgs& a) {
+    FAISS_THROW_IF_NOT_FMT(a.pq.nbits >= 4 && a.pq.nbits <= 8, "IVF-PQ nbits = %d not in [4, 8]",
+                           a.pq.nbits);
+    const size_t lds = sizeof(float) * ex_pq_table_floats(a.pq.M, a.pq.nbits, a.ldx);
+    FAISS_THROW_IF_NOT_FMT(lds <= 160 * 1024,
+                           "IVF-PQ table of M = %d, nbits = %d does not fit in LDS", a.pq.M,
+                           a.pq.nbits);
+    return lds;
+}
+
 }  // namespace
 
 // (query, probe) work groups per launch of the k_ex_* scans: 2^20 x 256
@@ -471,23 +431,27 @@ void ivf_exact_search(const ExactScanArgs& a, uint32_t* eoff, uint32_t* total, u
     if (a.sq.qtype >= 0) {
         ivf_exact_sq_scan(a, eoff, cap, keys, rows, s);
     } else if (a.pq.M > 0) {
-        const size_t lds = sizeof(float) * ((size_t)a.pq.M * 256 + 2 * (size_t)a.ldx + 1);
-        FAISS_THROW_IF_NOT_FMT(lds <= 160 * 1024, "IVF-PQ table of M = %d does not fit in LDS",
-                               a.pq.M);
-        const void* kfn = a.l2 ? (const void*)k_ex_pq<true> : (const void*)k_ex_pq<false>;
+        const size_t lds = ex_pq_lds(a);
+        const bool b8 = a.pq.nbits == 8;
+        const void* kfn = a.l2 ? (b8 ? (const void*)k_ex_pq<true, 8> : (const void*)k_ex_pq<true, 0>)
+                               : (b8 ? (const void*)k_ex_pq<false, 8>
+                                     : (const void*)k_ex_pq<false, 0>);
         if (lds > 64 * 1024)
             HIP_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)lds));
-#define EXPQ(L2)                                                                             \
-    k_ex_pq<L2><<<kgrid(ne, 256), dim3(256), lds, s>>>(                                     \
+#define EXPQ(L2, NB)                                                                         \
+    k_ex_pq<L2, NB><<<kgrid(ne, 256), dim3(256), lds, s>>>(                                 \
             a.x, a.ldx, a.d, a.np, a.assign, a.cdis, a.lim, a.list_off, a.list_len, a.nlist, \
             a.pq, a.sel, eoff, cap, keys, rows, e0)
         for (int64_t e0 = 0; e0 < entries; e0 += kExEntriesPerLaunch) {
             const int64_t ne = std::min(kExEntriesPerLaunch, entries - e0);
-            if (a.l2)
-                EXPQ(true);
-            else
-                EXPQ(false);
+            if (a.l2) {
+                if (b8) EXPQ(true, 8);
+                else EXPQ(true, 0);
+            } else {
+                if (b8) EXPQ(false, 8);
+                else EXPQ(false, 0);
+            }
         }
 #undef EXPQ
     } else {
@@ -516,21 +480,26 @@ void ivfpq_range_exact(const ExactScanArgs& a, float radius, uint32_t* counts,
     if (a.n <= 0 || a.np <= 0) return;
     const int64_t entries = a.n * (int64_t)a.np;
     FAISS_THROW_IF_NOT(entries < ((int64_t)1 << 31) && a.pq.M > 0);
-    const size_t lds = sizeof(float) * ((size_t)a.pq.M * 256 + 2 * (size_t)a.ldx + 1);
-    FAISS_THROW_IF_NOT_FMT(lds <= 160 * 1024, "IVF-PQ table of M = %d does not fit in LDS",
-                           a.pq.M);
-#define EXR(L2, F)                                                                            \
+    const size_t lds = ex_pq_lds(a);
+#define EXR_(L2, F, NB)                                                                       \
     do {                                                                                      \
         if (lds > 64 * 1024)                                                                  \
-            HIP_CHECK(hipFuncSetAttribute((const void*)k_ex_pq_range<L2, F>,                  \
+            HIP_CHECK(hipFuncSetAttribute((const void*)k_ex_pq_range<L2, F, NB>,              \
                                           hipFuncAttributeMaxDynamicSharedMemorySize,         \
                                           (int)lds));                                         \
         for (int64_t e0 = 0; e0 < entries; e0 += kExEntriesPerLaunch)                        \
-            k_ex_pq_range<L2, F>                                                              \
+            k_ex_pq_range<L2, F, NB>                                                          \
                     <<<kgrid(std::min(kExEntriesPerLaunch, entries - e0), 256), dim3(256), lds, \
                        s>>>(a.x, a.ldx, a.d, a.np, a.assign, a.cdis, a.list_off, a.list_len,  \
                             a.nlist, a.pq, radius, a.sel, a.ids, a.row_list, a.store_pairs,   \
                             counts, offsets, outD, outI, e0);                                 \
+    } while (0)
+#define EXR(L2, F)           \
+    do {                     \
+        if (a.pq.nbits == 8) \
+            EXR_(L2, F, 8);  \
+        else                 \
+            EXR_(L2, F, 0);  \
     } while (0)
     if (a.l2) {
         if (offsets) EXR(true, true);
@@ -540,6 +509,7 @@ void ivfpq_range_exact(const ExactScanArgs& a, float radius, uint32_t* counts,
         else EXR(false, false);
     }
 #undef EXR
+#undef EXR_
     HIP_LAUNCH_CHECK();
 }
 

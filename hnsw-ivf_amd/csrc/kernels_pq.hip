@@ -23,7 +23,7 @@ namespace faiss_amd {
 namespace kern {
 
 // ---------------------------------------------------------------- terms
-__global__ void k_ivfpq_terms(const uint8_t* __restrict__ codes, int code_stride,
+__global__ void k_ivfpq_terms(const uint8_t* __restrict__ codes, int code_stride, int nbits,
                               const uint32_t* __restrict__ row_list, int64_t nrows,
                               const float* __restrict__ cent, int ldcent,
                               const float* __restrict__ pq_cent, int M, int ksub, int dsub,
@@ -39,7 +39,8 @@ __global__ void k_ivfpq_terms(const uint8_t* __restrict__ codes, int code_stride
     const uint8_t* c = codes + row * code_stride;
     float s = 0.f;
     for (int m = 0; m < M; m++) {
-        const float* cm = pq_cent + ((int64_t)m * ksub + c[m]) * dsub;
+        const int j = nbits == 8 ? c[m] : pq_index(c, m, nbits);
+        const float* cm = pq_cent + ((int64_t)m * ksub + j) * dsub;
         const float* ym = yc + m * dsub;
         float nrm = 0.f, ip = 0.f;
         for (int i = 0; i < dsub; i++) {
@@ -51,14 +52,15 @@ __global__ void k_ivfpq_terms(const uint8_t* __restrict__ codes, int code_stride
     terms[row] = s;
 }
 
-void ivfpq_terms(const uint8_t* codes, const uint32_t* row_list, int64_t nrows,
-                 const float* centroids, int ldcent, const float* pq_centroids, int M, int ksub,
-                 int dsub, float* terms, hipStream_t s) {
+void ivfpq_terms(const uint8_t* codes, int code_stride, int nbits, const uint32_t* row_list,
+                 int64_t nrows, const float* centroids, int ldcent, const float* pq_centroids,
+                 int M, int ksub, int dsub, float* terms, hipStream_t s) {
     if (nrows <= 0) return;
-    const int code_stride = (int)roundup((size_t)M, 4);
+    FAISS_THROW_IF_NOT(nbits >= 4 && nbits <= 8 && ksub == 1 << nbits &&
+                       code_stride >= (M * nbits + 7) / 8);
     k_ivfpq_terms<<<kgrid(cdiv(nrows, 256), 256), dim3(256), 0, s>>>(
-            codes, code_stride, row_list, nrows, centroids, ldcent, pq_centroids, M, ksub, dsub,
-            terms);
+            codes, code_stride, nbits, row_list, nrows, centroids, ldcent, pq_centroids, M, ksub,
+            dsub, terms);
     HIP_LAUNCH_CHECK();
 }
 
@@ -156,7 +158,7 @@ void pq_encode(const float* x, int ldx, int64_t n, const int32_t* assign, const 
                hipStream_t s) {
     if (n <= 0) return;
     FAISS_THROW_IF_NOT(ksub <= 256);
-    // the 8-lane argmin assumes whole 8-row groups (ksub = 256 for nbits = 8)
+    // the 8-lane argmin assumes whole 8-row groups (ksub = 16 .. 256 for nbits 4 .. 8)
     FAISS_THROW_IF_NOT(ksub % 8 == 0);
     const int code_stride = (int)roundup((size_t)M, 4);
     const dim3 grid((unsigned)cdiv(n, 256), (unsigned)M);

@@ -111,5 +111,26 @@ __device__ __forceinline__ float pq_code_sum(int M, TF&& T) {
     return r;
 }
 
+// Index m of a packed code, PQDecoderGeneric (faiss/impl/ProductQuantizer-inl.h:
+// 57-97): bits [m * nbits, (m + 1) * nbits) of the little-endian bit stream,
+// 4 <= nbits <= 8.  Reads the second byte only when the index crosses into it,
+// so never past the row's (M * nbits + 7) / 8 code bytes.
+__device__ __forceinline__ int pq_index(const uint8_t* __restrict__ code, int m, int nbits) {
+    const int o = m * nbits, sh = o & 7;
+    uint32_t v = code[o >> 3];
+    if (sh + nbits > 8) v |= (uint32_t)code[(o >> 3) + 1] << 8;
+    return (int)((v >> sh) & ((1u << nbits) - 1u));
+}
+
+// Code sum of every decoder but PQDecoder8: distance_single_code_generic /
+// distance_four_codes_generic (faiss/impl/code_distance/code_distance-generic.h:
+// 16-79), a plain chain r = 0; r += tab[idx_m] for m = 0..M-1.
+template <class TF>
+__device__ __forceinline__ float pq_code_sum_seq(int M, TF&& T) {
+    float r = 0.f;
+    for (int m = 0; m < M; m++) r += T(m);
+    return r;
+}
+
 }  // namespace kern
 }  // namespace faiss_amd

@@ -823,6 +823,9 @@ struct IndexIVFPQ : IndexIVF {
     // M = d / 2: HBM spent to take the decode out of the filter's loop)
     mutable DeviceBuffer d_pcbs_;
     mutable bool pq_stream_ready_ = false;
+    // LDS-table list scan of packed codes, nbits < 8 (kernels_pq_lut.hip): per
+    // query a bound, a counter and the candidates under the bound
+    mutable DeviceBuffer s_lut_;
 };
 
 // faiss/impl/ScalarQuantizer.h:26-98.  QT_8bit and QT_fp16 with d % 8 == 0 are
