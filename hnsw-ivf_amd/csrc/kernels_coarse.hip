@@ -732,12 +732,23 @@ __global__ __launch_bounds__(64, CR_WAVES) void k_coarse_rerank(
     const bool has = lane * V < E;
 #pragma unroll
     for (int i = 0; i < V; i++) kv[i] = has ? kq[lane * V + i] : 0xffffffffu;
-    const float my_pb = (valid && lane < NST) ? pbs[q * NST + lane] : WS_INF;
+    float my_pb = (valid && lane < NST) ? pbs[q * NST + lane] : WS_INF;
     const float xn = xnorm ? xnorm[q] : 0.f;
     const float* xq = x + q * ldx;
     if (lane < BDM / 4 && 4 * lane < ((d + 3) & ~3))
         *(float4*)(&xsh[4 * lane]) = *(const float4*)(xq + 4 * lane);
-    const float M = coarse_margin(xn, cnmax_p, coef, y3 != 0);
+    float M = coarse_margin(xn, cnmax_p, coef, y3 != 0);
+    // a non-finite row (cnmax = +inf, k_array_max) or a non-finite query:
+    // approximations may be NaN, which no bracket holds.  No key counts and
+    // every stream counts as failed, so every row is evaluated exactly and
+    // the admission rule decides (a NaN or infinite distance never enters
+    // the reference's heap).
+    if (!(M < WS_INF)) {
+#pragma unroll
+        for (int i = 0; i < V; i++) kv[i] = 0xffffffffu;
+        if (valid && lane < NST) my_pb = -WS_INF;
+        M = 0.f;
+    }
     // ---- U
     float ub[V];
 #pragma unroll
@@ -896,7 +907,11 @@ __global__ __launch_bounds__(64, CR_WAVES) void k_coarse_rerank(
 __global__ void k_array_max(const float* __restrict__ a, int64_t n, float* __restrict__ out) {
     __shared__ float red[16];
     float m = 0.f;
-    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) m = fmaxf(m, a[i]);
+    // (a non-finite entry makes the maximum +inf: fmaxf alone drops a NaN)
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
+        const float v = a[i];
+        m = v < WS_INF ? fmaxf(m, v) : WS_INF;
+    }
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) m = fmaxf(m, __shfl_xor(m, s));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;

@@ -267,6 +267,19 @@ __global__ __launch_bounds__(256, Y3 ? 2 : 3) void k_ivf_bf3_filter(
     }
     __syncthreads();
     if (qvalid) {
+        // the list's largest margin bounds every kept row's margin:
+        // Y3: coef (x^2 + y^2); bf16x2: Cauchy-Schwarz on the code
+        // rounding residual, 2 (2 |x| |y - yh| + coef (x^2 + y^2))
+        const float mmax = Y3 ? coef * (xn + ynmax[l]) + 1e-30f
+                              : 2.f * (2.f * sqrtf(xn) * rmax[l] + coef * (xn + ynmax[l])) +
+                                        1e-30f;
+        // a non-finite row in the list (ynmax = +inf, k_list_max) or a
+        // non-finite query: approximations may be NaN, which no bracket
+        // holds.  Such a (query, list) keeps no key and reports every stream
+        // as having dropped rows of any value, so the re-rank evaluates the
+        // whole list exactly and its admission rule decides (the reference's:
+        // a NaN or infinite distance never enters the heap).
+        const bool taint = !(mmax < WS_INF);
         // raw 32-bit keys (the re-rank decodes the approx bracket and the row)
         const int64_t e = ent_s[qloc];
         // max_codes: only a prefix of the list is scanned for this query
@@ -282,26 +295,21 @@ __global__ __launch_bounds__(256, Y3 ? 2 : 3) void k_ivf_bf3_filter(
                 const int r = (int)(ord & 15u);
                 const uint32_t row = (ord >> 4) * BV + 32 * bi + 4 * lh + 8 * (r >> 2) + (r & 3);
                 if constexpr (HS)
-                    ko[i] = (key != 0xffffffffu && row < elen && sel[row0 + row]) ? key
-                                                                                   : 0xffffffffu;
+                    ko[i] = (key != 0xffffffffu && row < elen && sel[row0 + row] && !taint)
+                                    ? key
+                                    : 0xffffffffu;
                 else
-                    ko[i] = (key != 0xffffffffu && row < elen) ? key : 0xffffffffu;
+                    ko[i] = (key != 0xffffffffu && row < elen && !taint) ? key : 0xffffffffu;
             }
         }
         if (lh == 0) {
-            // the list's largest margin bounds every kept row's margin:
-            // Y3: coef (x^2 + y^2); bf16x2: Cauchy-Schwarz on the code
-            // rounding residual, 2 (2 |x| |y - yh| + coef (x^2 + y^2))
-            const float mmax = Y3 ? coef * (xn + ynmax[l]) + 1e-30f
-                                  : 2.f * (2.f * sqrtf(xn) * rmax[l] + coef * (xn + ynmax[l])) +
-                                            1e-30f;
             ProbeRec pr;
 #pragma unroll
             for (int sl = 0; sl < 4; sl++) {
                 const float b = bnd_s[qloc][sl];
-                pr.pb[sl] = b < WS_INF ? b - mmax : WS_INF;
+                pr.pb[sl] = taint ? -WS_INF : b < WS_INF ? b - mmax : WS_INF;
             }
-            pr.mmax = mmax;
+            pr.mmax = taint ? 0.f : mmax;
             pr.off = (uint32_t)row0;
             pr.len = elen;
             pr.pad = 0u;
@@ -660,6 +668,18 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_ivf_bf2_stream(
     if (qvalid) {
         const int64_t e = my_e;
         const uint32_t elen = min((uint32_t)len, lim_e);
+        float mmax;
+        if constexpr (PQ) {
+            // 2 |x| r + coef (|x| + |y_C| + R)^2 (k_ivfpq_filter_w), doubled
+            const float xl = sqrtf(xn);
+            const float sr = xl + cnorm_l + ynmax_l;
+            mmax = 2.f * (2.f * xl * rmax_l + coef * sr * sr) + 1e-30f;
+        } else {
+            mmax = 2.f * (2.f * sqrtf(xn) * rmax_l + coef * (xn + ynmax_l)) + 1e-30f;
+        }
+        // a non-finite row in the list or a non-finite query: no key is kept
+        // and every stream counts as failed (see k_ivf_bf3_filter)
+        const bool taint = !(mmax < WS_INF);
 #pragma unroll
         for (int bi = 0; bi < 2; bi++) {
             uint32_t* ko = keys + e * (4 * KT) + (2 * bi + lh) * KT;
@@ -669,25 +689,16 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_ivf_bf2_stream(
                 const uint32_t ord = key & lowmask;
                 const int r = (int)(ord & 15u);
                 const uint32_t row = (ord >> 4) * BV + 32 * bi + 4 * lh + 8 * (r >> 2) + (r & 3);
-                ko[i] = (key != 0xffffffffu && row < elen) ? key : 0xffffffffu;
+                ko[i] = (key != 0xffffffffu && row < elen && !taint) ? key : 0xffffffffu;
             }
         }
         if (lh == 0) {
-            float mmax;
-            if constexpr (PQ) {
-                // 2 |x| r + coef (|x| + |y_C| + R)^2 (k_ivfpq_filter_w), doubled
-                const float xl = sqrtf(xn);
-                const float sr = xl + cnorm_l + ynmax_l;
-                mmax = 2.f * (2.f * xl * rmax_l + coef * sr * sr) + 1e-30f;
-            } else {
-                mmax = 2.f * (2.f * sqrtf(xn) * rmax_l + coef * (xn + ynmax_l)) + 1e-30f;
-            }
             ProbeRec pr;
             const float bb4[4] = {bnd2[0], bnd_p0, bnd2[1], bnd_p1};  // slots 0..3
 #pragma unroll
             for (int sl = 0; sl < 4; sl++)
-                pr.pb[sl] = bb4[sl] < WS_INF ? bb4[sl] - mmax : WS_INF;
-            pr.mmax = mmax;
+                pr.pb[sl] = taint ? -WS_INF : bb4[sl] < WS_INF ? bb4[sl] - mmax : WS_INF;
+            pr.mmax = taint ? 0.f : mmax;
             pr.off = (uint32_t)row0;
             pr.len = elen;
             pr.pad = PQ ? (uint32_t)l : 0u;  // the PQ re-rank's list
@@ -874,7 +885,13 @@ __global__ void k_list_max(const float* __restrict__ yn, const uint32_t* __restr
     const int l = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (l >= nlist) return;
     float m = 0.f;
-    for (uint32_t i = lane; i < len[l]; i += 64) m = fmaxf(m, yn[off[l] + i]);
+    // (fmaxf drops a NaN: a non-finite entry, the norm of a row with a NaN or
+    // infinite coordinate, makes the maximum +inf, and with it every margin
+    // of the list)
+    for (uint32_t i = lane; i < len[l]; i += 64) {
+        const float v = yn[off[l] + i];
+        m = v < WS_INF ? fmaxf(m, v) : WS_INF;
+    }
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) m = fmaxf(m, __shfl_xor(m, s));
     if (lane == 0) out[l] = m;

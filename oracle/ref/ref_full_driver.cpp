@@ -228,6 +228,13 @@ int reff_encode_vectors(void* h, int64_t n, const float* x, const int64_t* list_
     return guarded([&] { ivf_of(h)->encode_vectors(n, x, list_nos, codes, false); });
 }
 
+// IndexIVF::add_core with the caller's list numbers (rows a coarse quantizer
+// would not assign, e.g. non-finite ones, placed in chosen lists)
+int reff_add_core(void* h, int64_t n, const float* x, const int64_t* ids,
+                  const int64_t* list_nos) {
+    return guarded([&] { ivf_of(h)->add_core(n, x, ids, list_nos); });
+}
+
 int64_t reff_list_size(void* h, int64_t l) { return ivf_of(h)->invlists->list_size(l); }
 int reff_list_copy(void* h, int64_t l, uint8_t* codes, int64_t* ids) {
     return guarded([&] {
