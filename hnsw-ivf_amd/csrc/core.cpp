@@ -532,6 +532,119 @@ void IndexFlat::search_selected(idx_t n, const float* x, int ldx, idx_t k, float
     order_.leave(s);
 }
 
+// faiss/IndexFlat.cpp:71-90 -> faiss/utils/distances.cpp:940-966 with a
+// RangeSearchBlockResultHandler: a selector or fewer than 20 queries take the
+// direct form over is_member (no IDSelectorRange / IDSelectorArray special
+// case here, unlike k-NN), anything else the BLAS form; hits of a query in
+// ascending row order, strict comparison, only params->sel is read.  All the
+// buffers are locals: two passes per query chunk (kernels_flat_range.hip).
+void IndexFlat::range_search(idx_t n, const float* x, float radius, RangeSearchResult* result,
+                             const SearchParameters* params) const {
+    FAISS_THROW_IF_NOT(n >= 0 && result && result->nq == (size_t)n);
+    result->lims.assign((size_t)n + 1, 0);
+    result->labels.clear();
+    result->distances.clear();
+    if (n == 0 || ntotal == 0) return;
+    DeviceGuard dg(device);
+    sync_device();
+    hipStream_t s = stream();
+    std::lock_guard<std::recursive_mutex> g(mu_);
+    const int l = ld();
+    const int metric_l2 = metric_type == METRIC_L2;
+    const IDSelector* sel = params ? params->sel : nullptr;
+    const bool direct = sel != nullptr || n < 20;
+    const idx_t ny = ntotal;
+    // (query, block of rows) cells of the count scratch, within the tile
+    // budget of knn_impl.  A chunk is never below one tile row (128 queries,
+    // BLAS form) or one query (direct form): past 67M rows (BLAS form) the
+    // floor holds and the counts are 128 x ntotal / 128 x 4 B = 4 B per
+    // database row, above the budget but still independent of n
+    const idx_t nblk =
+            (idx_t)cdiv((size_t)ny, direct ? kern::kFlatRangeRows : kern::kFlatRangeTile);
+    const idx_t qgran = direct ? 1 : kern::kFlatRangeTile;
+    const size_t count_budget = (size_t)256 << 20;  // bytes
+    idx_t qc = (idx_t)(count_budget / (sizeof(uint32_t) * nblk)) / qgran * qgran;
+    qc = std::min<idx_t>(std::max<idx_t>(qc, qgran), n);
+    DeviceBuffer bx, bxn, bmask, bc, bo, bd, bi;
+    std::vector<uint32_t> cnt;
+    std::vector<uint64_t> offs;
+    order_.enter(s);
+    try {
+        bx.reserve(sizeof(float) * n * l);
+        if (l != d) HIP_CHECK(hipMemsetAsync(bx.ptr, 0, sizeof(float) * n * l, s));
+        HIP_CHECK(hipMemcpy2DAsync(bx.ptr, sizeof(float) * l, x, sizeof(float) * d,
+                                   sizeof(float) * d, n, hipMemcpyHostToDevice, s));
+        const uint8_t* mask = nullptr;
+        if (sel) {
+            const idx_t* ids = device_row_ids(s);
+            bmask.reserve((size_t)ny);
+            sel->mark_device(ids, ny, bmask.as<uint8_t>(), s);
+            mask = bmask.as<uint8_t>();
+        }
+        if (metric_l2 && !direct) {
+            // the norms of the BLAS-form k-NN path (knn_impl)
+            bxn.reserve(sizeof(float) * n);
+            kern::row_norms(bx.as<float>(), n, d, l, bxn.as<float>(), s);
+        }
+        bc.reserve(sizeof(uint32_t) * qc * nblk);
+        for (idx_t q0 = 0; q0 < n; q0 += qc) {
+            const idx_t nc = std::min(qc, n - q0);
+            const size_t m = (size_t)nc * nblk;
+            const float* xq = bx.as<float>() + (size_t)q0 * l;
+            const float* xn = metric_l2 && !direct ? bxn.as<float>() + q0 : nullptr;
+            auto launch = [&](uint32_t* counts, const uint64_t* offsets, float* D, idx_t* I) {
+                ScopedKernelTimer tm(&ktimes, "flat_range", 2.0 * nc * ny * d, s);
+                if (direct)
+                    kern::flat_range_direct(xq, nc, l, d_xb_.as<float>(), ny, l, d, metric_l2,
+                                            radius, mask, counts, offsets, D, I, s);
+                else
+                    kern::flat_range_tile(xq, nc, l, xn, d_xb_.as<float>(), ny, l,
+                                          d_norms_.as<float>(), l, metric_l2, radius, counts,
+                                          offsets, D, I, s);
+            };
+            launch(bc.as<uint32_t>(), nullptr, nullptr, nullptr);
+            cnt.resize(m);
+            HIP_CHECK(hipMemcpyAsync(cnt.data(), bc.ptr, sizeof(uint32_t) * m,
+                                     hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            // query-major, blocks of rows ascending within a query
+            offs.resize(m);
+            const size_t base = result->labels.size();
+            uint64_t tot = 0;
+            for (idx_t i = 0; i < nc; i++) {
+                result->lims[(size_t)(q0 + i)] = base + tot;
+                const size_t j0 = (size_t)i * nblk;
+                for (idx_t b = 0; b < nblk; b++) {
+                    offs[j0 + b] = tot;
+                    tot += cnt[j0 + b];
+                }
+            }
+            if (tot) {
+                bo.reserve(sizeof(uint64_t) * m);
+                bd.reserve(sizeof(float) * tot);
+                bi.reserve(sizeof(idx_t) * tot);
+                HIP_CHECK(hipMemcpyAsync(bo.ptr, offs.data(), sizeof(uint64_t) * m,
+                                         hipMemcpyHostToDevice, s));
+                launch(nullptr, bo.as<uint64_t>(), bd.as<float>(), bi.as<idx_t>());
+                result->labels.resize(base + tot);
+                result->distances.resize(base + tot);
+                HIP_CHECK(hipMemcpyAsync(result->distances.data() + base, bd.ptr,
+                                         sizeof(float) * tot, hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipMemcpyAsync(result->labels.data() + base, bi.ptr,
+                                         sizeof(idx_t) * tot, hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+            }
+            // the reference polls after each query block (distances.cpp:252, 340)
+            InterruptCallback::check();
+        }
+    } catch (...) {
+        order_.leave(s);
+        throw;
+    }
+    order_.leave(s);
+    result->lims[(size_t)n] = result->labels.size();
+}
+
 void IndexFlat::assign_device(idx_t n, const float* x, int ldx, int k, float* distances,
                               int32_t* labels, const SearchParameters*, hipStream_t s) const {
     DeviceGuard g(device);

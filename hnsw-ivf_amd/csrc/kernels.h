@@ -510,5 +510,24 @@ void ivf_range_flat(const float* x, int64_t n, int ldx, const int32_t* assign, i
                     const uint8_t* selm, uint32_t* counts, const uint64_t* offsets, float* outD,
                     int64_t* outI, hipStream_t s);
 
+// IndexFlat range search (kernels_flat_range.hip), two passes each:
+// offsets == nullptr counts the hits (dis < radius for L2, > for IP) of every
+// (query, block of rows); else the hits (distance, row number) are written at
+// that block's offset, in ascending row order.  x, y, xn, yn: device.
+// BLAS form on pairwise_distances' fp32-MFMA tile, thresholded in registers:
+// blocks of kFlatRangeTile rows, counts/offsets[q * cdiv(ny, kFlatRangeTile) + b].
+constexpr int kFlatRangeTile = 128;
+void flat_range_tile(const float* x, int64_t nx, int ldx, const float* xn, const float* y,
+                     int64_t ny, int ldy, const float* yn, int dp, int metric_l2, float radius,
+                     uint32_t* counts, const uint64_t* offsets, float* outD, int64_t* outI,
+                     hipStream_t s);
+// Direct form (ref_arith.h per pair) over the rows the mask admits (selm ==
+// nullptr: all): blocks of kFlatRangeRows rows, one wave per (query, block),
+// counts/offsets[q * cdiv(ny, kFlatRangeRows) + b].
+constexpr int kFlatRangeRows = 1024;
+void flat_range_direct(const float* x, int64_t nx, int ldx, const float* y, int64_t ny, int ldy,
+                       int d, int metric_l2, float radius, const uint8_t* selm, uint32_t* counts,
+                       const uint64_t* offsets, float* outD, int64_t* outI, hipStream_t s);
+
 }  // namespace kern
 }  // namespace faiss_amd

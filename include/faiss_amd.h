@@ -237,7 +237,8 @@ struct Index {
     virtual void reset() = 0;
     virtual void reconstruct(idx_t key, float* recons) const;
     // faiss/Index.h:183-196: all vectors with distance < radius (L2) or
-    // > radius (IP); only IndexIVFFlat implements it on this path
+    // > radius (IP), strictly.  IndexFlat, IndexIVFFlat, IndexIVFPQ and an
+    // IndexRefine over any of them implement it; the others throw
     virtual void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result,
                               const SearchParameters* params = nullptr) const;
     virtual void sync_device() const {}
@@ -279,6 +280,11 @@ struct IndexFlat : Index {
     void reset() override;
     void reconstruct(idx_t key, float* recons) const override;
     void sync_device() const override;
+    // faiss/IndexFlat.cpp:71-90: hits of a query in ascending row order; the
+    // BLAS form for >= 20 queries without a selector, else the direct form
+    // over the selector's members.  Only params->sel is read.
+    void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result,
+                      const SearchParameters* params = nullptr) const override;
 
     const float* device_vectors() const;  // [ntotal][ld]
     const float* device_norms() const;
