@@ -223,8 +223,9 @@ void IndexIVF::sync_device() const {
     d_codes_.reserve(code_bytes + sizeof(float) * kern::BDM_HOST);
     d_ids_.reserve(sizeof(idx_t) * hi.size());
     d_row_list_.reserve(sizeof(uint32_t) * hl.size());
-    d_list_off_.reserve(sizeof(uint32_t) * (nlist + 1));
-    d_list_len_.reserve(sizeof(uint32_t) * std::max<size_t>(nlist, 1));
+    // (the per-list arrays are whole uint4 groups: kern::ivf_bucket reads them so)
+    d_list_off_.reserve(sizeof(uint32_t) * roundup(nlist + 1, 4));
+    d_list_len_.reserve(sizeof(uint32_t) * roundup(std::max<size_t>(nlist, 1), 4));
     // Codes: packed arena order into two pinned staging buffers, each copied
     // to HBM while the other fills (no whole-arena host image; mapped lists
     // are read from the page cache exactly once).
@@ -295,7 +296,7 @@ void IndexIVF::sync_device() const {
         for (size_t l = 0; l < nlist; l++) perm[l] = (uint32_t)l;
         std::stable_sort(perm.begin(), perm.end(),
                          [&](uint32_t a, uint32_t b) { return len[a] > len[b]; });
-        d_list_perm_.reserve(sizeof(uint32_t) * std::max<size_t>(nlist, 1));
+        d_list_perm_.reserve(sizeof(uint32_t) * roundup(std::max<size_t>(nlist, 1), 4));
         HIP_CHECK(hipMemcpyAsync(d_list_perm_.ptr, perm.data(), sizeof(uint32_t) * nlist,
                                  hipMemcpyHostToDevice, s));
         HIP_CHECK(hipStreamSynchronize(s));  // perm is a host temporary
@@ -306,20 +307,31 @@ void IndexIVF::sync_device() const {
     version_++;  // (the content uploaded may differ from what a captured graph saw)
 }
 
+namespace {
+// s_ictr_: the filters' work counter, the fill's ticket (word 1; 2 and 3
+// free), then the many-group scan's block totals
+constexpr size_t kIctrBytes = 16 + 4 * 3 * 64;
+}  // namespace
+
 uint32_t* IndexIVF::bucket_counts(hipStream_t s, uint32_t** next) const {
-    // nlist counters, zero between calls: the scan clears each count once it
-    // has read it (self-cleaning, so a captured step can be replayed).  A
-    // (re)allocation starts them at zero; they are (re)zeroed as well when
-    // the previous call did not reach flip_counts() (an exception between
-    // the two left them dirty) or ran on another stream (whose scan may still
-    // be clearing them)
-    const size_t need = sizeof(uint32_t) * std::max<size_t>(nlist, 1);
-    const bool fresh = !s_counts_.ptr || s_counts_.bytes < need;
+    // nlist counters, zero between calls: the bucket kernel that reads them
+    // last clears them (self-cleaning, so a captured step can be replayed),
+    // and the fill's ticket word beside the work counter returns to zero the
+    // same way.  A (re)allocation starts both at zero; they are (re)zeroed as
+    // well when the previous call did not reach flip_counts() (an exception
+    // between the two left them dirty) or ran on another stream (whose
+    // kernels may still be clearing them)
+    // (whole uint4 groups: kern::ivf_bucket reads the per-list arrays so)
+    const size_t need = sizeof(uint32_t) * roundup(std::max<size_t>(nlist, 1), 4);
+    const bool fresh = !s_counts_.ptr || s_counts_.bytes < need || !s_ictr_.ptr ||
+                       s_ictr_.bytes < kIctrBytes;
     if (fresh || counts_pending_ || s != counts_stream_) {
         if (!fresh && s != counts_stream_ && counts_stream_valid_)
             HIP_CHECK(hipStreamSynchronize(counts_stream_));
         s_counts_.reserve(need);
+        s_ictr_.reserve(kIctrBytes);
         HIP_CHECK(hipMemsetAsync(s_counts_.ptr, 0, need, s));
+        HIP_CHECK(hipMemsetAsync(s_ictr_.as<uint32_t>() + 1, 0, sizeof(uint32_t), s));
         counts_parity_ = 0;
     }
     counts_stream_ = s;
@@ -1411,9 +1423,10 @@ void IndexIVFFlat::search_preassigned_device(idx_t n, const float* x, int ldx, i
     s_ient_.reserve(sizeof(uint32_t) * max_items * QT);
     b.item_desc = s_idesc_.as<kern::ItemDesc>();
     b.item_entries = s_ient_.as<uint32_t>();
-    s_ictr_.reserve(16 + 4 * 3 * 64);
+    s_ictr_.reserve(kIctrBytes);
     b.item_ctr = s_ictr_.as<uint32_t>();
     b.scan_tmp = s_ictr_.as<uint32_t>() + 4;
+    b.ticket = s_ictr_.as<uint32_t>() + 1;
     {
         ScopedKernelTimer tb(&ktimes, "ivf_bucket", 0.0, s);
         kern::ivf_bucket(assign, n, np, d_list_len_.as<uint32_t>(), d_list_off_.as<uint32_t>(),
@@ -1752,9 +1765,10 @@ void IndexIVFPQ::search_preassigned_device(idx_t n, const float* x, int ldx, idx
         s_ent_.reserve(sizeof(uint32_t) * n * np);
         kern::IVFBuckets b{counts, s_boff_.as<uint32_t>(), s_ioff_.as<uint32_t>(),
                            s_cur_.as<uint32_t>(), s_ent_.as<uint32_t>()};
-        s_ictr_.reserve(16 + 4 * 3 * 64);
+        s_ictr_.reserve(kIctrBytes);
         b.item_ctr = s_ictr_.as<uint32_t>();  // the PQ filter's work counter
         b.scan_tmp = s_ictr_.as<uint32_t>() + 4;
+        b.ticket = s_ictr_.as<uint32_t>() + 1;
         b.counts_next = counts_next;
         b.lim = lim;
         b.sel = sel;
@@ -1853,7 +1867,7 @@ void IndexIVFPQ::search_preassigned_device(idx_t n, const float* x, int ldx, idx
         const int64_t mi = kern::ivf_max_items(qc, np, (int)nlist, QT);
         s_idesc_.reserve(sizeof(kern::ItemDesc) * mi);
         s_ient_.reserve(sizeof(uint32_t) * mi * QT);
-        s_ictr_.reserve(16 + 4 * 3 * 64);
+        s_ictr_.reserve(kIctrBytes);
         kern::ExactScanArgs a;
         exact_args(&a);
         a.ldx = ldx;
@@ -1879,6 +1893,7 @@ void IndexIVFPQ::search_preassigned_device(idx_t n, const float* x, int ldx, idx
                                s_cur_.as<uint32_t>(), s_ent_.as<uint32_t>()};
             b.item_ctr = s_ictr_.as<uint32_t>();
             b.scan_tmp = s_ictr_.as<uint32_t>() + 4;
+            b.ticket = s_ictr_.as<uint32_t>() + 1;
             b.counts_next = counts_next;
             b.lim = a.lim;
             b.sel = sel;

@@ -131,6 +131,9 @@ struct IVFBuckets {
     uint32_t* item_list = nullptr;  // [max_items]: list of each work item
     uint32_t* item_ctr = nullptr;   // [1]: zeroed by the scan (persistent filter's counter)
     uint32_t* scan_tmp = nullptr;   // [3 * 64]: the many-group scan's block totals
+    // [1], zero between calls: the ticket of the fill that scans the counts
+    // itself (its last work group clears the counts); nullptr = scan kernel
+    uint32_t* ticket = nullptr;
     // optional: lists by decreasing length; work items are numbered in this
     // order (longest first: the filters' launch order, so the long items do
     // not start last and set the kernel's tail)
@@ -146,9 +149,10 @@ struct IVFBuckets {
     uint32_t* mark_keys = nullptr;
     ProbeRec* mark_recs = nullptr;
     int mark_ke = 0;
-    // optional: the count array the scan clears after reading it (== counts:
-    // self-cleaning).  When set, `counts` is already zero (the previous
-    // call's scan cleared it), so no memset is launched.
+    // optional: the count array the scan (or the scanning fill's last work
+    // group) clears after reading it (== counts: self-cleaning).  When set,
+    // `counts` is already zero (the previous call cleared it), so no memset
+    // is launched.
     uint32_t* counts_next = nullptr;
     // optional (max_codes): rows of each entry's list that are scanned (a
     // prefix; probe_limits), nullptr = whole lists
@@ -163,6 +167,8 @@ struct IVFBuckets {
 void probe_limits(const int32_t* assign, int64_t n, int nprobe, const uint32_t* list_len,
                   int nlist, int64_t max_codes, int32_t* assign_out, uint32_t* lim,
                   hipStream_t s);
+// Up to 8192 lists the per-list arrays (list_len, list_off, b.counts, b.perm)
+// are read as uint4 groups: their allocations hold a multiple of four words.
 void ivf_bucket(const int32_t* assign, int64_t n, int nprobe, const uint32_t* list_len,
                 const uint32_t* list_off, int nlist, int QT, IVFBuckets b, hipStream_t s);
 // the certified exact re-rank of the IVF-Flat filter's keys / probe records

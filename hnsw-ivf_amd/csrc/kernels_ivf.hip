@@ -435,6 +435,348 @@ __global__ void k_bucket_fill(const int32_t* __restrict__ assign, int64_t total,
     }
 }
 
+// ------------------------------------------------ the scan inside the fill
+// Up to BF_MAXL lists (and no item_list) the prefix sums of k_bucket_scan are
+// rebuilt in the LDS of every work group of the fill instead of by a launch
+// of their own: the scan kernel was one work group's launch, drain and two
+// dependent round trips on the critical path (c2: 8 us of a 270 us step) for
+// a few KB of traffic.  k_bucket_fill_scan follows k_bucket_count_lds (two
+// launches); k_bucket_one also builds the histogram, in one work group, for
+// batches of at most BF_ONE_MAX entries (one launch; c1: 8000).
+constexpr int BF_MAXL = 8192;           // E = 8 counts per thread, 4 x 32 KB of LDS
+constexpr int64_t BF_ONE_MAX = 16384;   // 16 entries per thread of one work group
+
+struct BFArgs {
+    const int32_t* assign;
+    int64_t total;
+    const uint32_t* list_len;
+    const uint32_t* list_off;
+    int nlist, QT;
+    uint32_t* bucket_off;
+    uint32_t* item_off;
+    uint32_t* item_ctr;
+    const uint32_t* perm;
+    uint32_t* entries;
+    uint32_t* item_entries;
+    ItemDesc* item_desc;
+    uint32_t* mkeys;
+    ProbeRec* mrecs;
+    int ke;
+};
+
+// What k_bucket_scan computes, for one work group of 1024 threads with the
+// counts in LDS (cnt, complete): c = this thread's counts of lists [E t,
+// E t + E) (0 past nlist), ls = the lists at [E t, E t + E) of the item order
+// (perm, or the identity; -1 past nlist).  off[l] becomes the first work item
+// of list l (item_entries given) or the first slot of its bucket (entries);
+// `global` also writes bucket_off, item_off and the work counter as the scan
+// kernel does.  off[] is complete for every thread on return (a barrier).
+template <int E>
+__device__ __forceinline__ void bf_offsets(const BFArgs& a, const uint32_t* cnt, uint32_t* off,
+                                           uint32_t* wb, uint32_t* wi, const uint32_t (&c)[E],
+                                           const int (&ls)[E], int qs, bool global) {
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, l0 = E * t;
+    const uint32_t QT = (uint32_t)a.QT;
+    auto nitems = [&](uint32_t v) -> uint32_t {
+        return qs >= 0 ? (v + QT - 1u) >> qs : (v + QT - 1u) / QT;
+    };
+    uint32_t n[E], sb = 0u, si = 0u;
+#pragma unroll
+    for (int j = 0; j < E; j++) {
+        n[j] = ls[j] >= 0 ? nitems(cnt[ls[j]]) : 0u;
+        sb += c[j];
+        si += n[j];
+    }
+    uint32_t ib = sb, ii = si;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t vb = __shfl_up(ib, o), vi = __shfl_up(ii, o);
+        if (lane >= o) {
+            ib += vb;
+            ii += vi;
+        }
+    }
+    if (lane == 63) {
+        wb[w] = ib;
+        wi[w] = ii;
+    }
+    __syncthreads();
+    uint32_t pb = ib - sb, pi = ii - si, tb = 0u, ti = 0u;
+#pragma unroll
+    for (int v = 0; v < 16; v++) {
+        pb += v < w ? wb[v] : 0u;
+        pi += v < w ? wi[v] : 0u;
+        tb += wb[v];
+        ti += wi[v];
+    }
+    uint32_t ob[E], oi[E];
+#pragma unroll
+    for (int j = 0; j < E; j++) {
+        ob[j] = pb;
+        oi[j] = pi;
+        pb += c[j];
+        pi += n[j];
+    }
+    if (a.item_entries) {
+#pragma unroll
+        for (int j = 0; j < E; j++)
+            if (ls[j] >= 0) off[ls[j]] = oi[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < E; j++)
+            if (l0 + j < a.nlist) off[l0 + j] = ob[j];
+    }
+    if (global) {
+        if (l0 + E <= a.nlist) {
+#pragma unroll
+            for (int v = 0; v < E / 4; v++)
+                *(uint4*)(a.bucket_off + l0 + 4 * v) =
+                        make_uint4(ob[4 * v], ob[4 * v + 1], ob[4 * v + 2], ob[4 * v + 3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < E; j++)
+                if (l0 + j < a.nlist) a.bucket_off[l0 + j] = ob[j];
+        }
+        if (!a.item_entries) {
+#pragma unroll
+            for (int j = 0; j < E; j++)
+                if (ls[j] >= 0) a.item_off[ls[j]] = oi[j];
+        }
+        if (t == 0) {
+            a.bucket_off[a.nlist] = tb;
+            a.item_off[a.nlist] = ti;
+            if (a.item_ctr) *a.item_ctr = 0u;  // the persistent filter's work counter
+        }
+    }
+    __syncthreads();
+    if (global && a.item_entries) {  // off[] is item_off by list: copied out coalesced
+        if (l0 + E <= a.nlist) {
+#pragma unroll
+            for (int v = 0; v < E / 4; v++)
+                *(uint4*)(a.item_off + l0 + 4 * v) =
+                        make_uint4(off[l0 + 4 * v], off[l0 + 4 * v + 1], off[l0 + 4 * v + 2],
+                                   off[l0 + 4 * v + 3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < E; j++)
+                if (l0 + j < a.nlist) a.item_off[l0 + j] = off[l0 + j];
+        }
+    }
+}
+
+// what k_bucket_fill stores for entry e of list l (-1: not a list) at slot p
+// of its bucket; geo = the lists' {length, arena offset} in LDS.  A list that
+// is probed by a valid entry has a count of at least one, and a list of
+// length 0 has none, so cnt[l] > 0 stands for the fill's list_len[l] > 0.
+__device__ __forceinline__ void bf_store(const BFArgs& a, const uint32_t* cnt, const uint32_t* off,
+                                         const uint2* geo, int qs, int64_t e, int l, uint32_t p) {
+    const uint32_t QT = (uint32_t)a.QT;
+    const uint32_t c = l >= 0 ? cnt[l] : 0u;
+    if (c) {
+        if (a.item_entries) {
+            const uint32_t pq = qs >= 0 ? p >> qs : p / QT, pr = p - pq * QT;
+            const uint32_t item = off[l] + pq;
+            a.item_entries[item * QT + pr] = (uint32_t)e;
+            if (pr == 0) {  // the item's first entry writes its descriptor
+                ItemDesc dsc;
+                dsc.l = (uint32_t)l;
+                dsc.nq = min(QT, c - p);
+                const uint2 g = geo[l];
+                dsc.len = g.x;
+                dsc.off = g.y;
+                a.item_desc[item] = dsc;
+            }
+        } else {
+            a.entries[off[l] + p] = (uint32_t)e;
+        }
+    } else if (a.mkeys) {
+        for (int i = 0; i < a.ke; i++) a.mkeys[e * a.ke + i] = 0xffffffffu;
+        ProbeRec pr;
+        for (int i = 0; i < 4; i++) pr.pb[i] = WS_INF;
+        pr.mmax = 0.f;
+        pr.off = 0u;
+        pr.len = 0u;
+        pr.pad = 0u;
+        a.mrecs[e] = pr;
+    }
+}
+
+// Words [E t, E t + E) of a per-list array, as uint4 groups and without a
+// branch: a load under a branch is waited for where the branch ends, and the
+// loads of these kernels are meant to be in flight together.  The arrays are
+// allocated in whole uint4 groups (IVFBuckets), so the group that holds the
+// last list may be read whole; a thread past it reads that group again, and
+// the caller masks what lies past nlist.
+template <int E>
+__device__ __forceinline__ void bf_load_words(const uint32_t* p, int nlist, uint32_t (&v)[E]) {
+    const int g0 = (E / 4) * (int)threadIdx.x, glast = (nlist + 3) / 4 - 1;
+#pragma unroll
+    for (int u = 0; u < E / 4; u++) {
+        const uint4 x = ((const uint4*)p)[min(g0 + u, glast)];
+        v[4 * u] = x.x;
+        v[4 * u + 1] = x.y;
+        v[4 * u + 2] = x.z;
+        v[4 * u + 3] = x.w;
+    }
+}
+// the lists at [E t, E t + E) of the item order from the words of perm (or
+// of any array when there is no perm: the identity), -1 past nlist
+template <int E>
+__device__ __forceinline__ void bf_item_order(bool has_perm, int nlist, const uint32_t (&pw)[E],
+                                              int (&ls)[E]) {
+    const int i0 = E * (int)threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < E; j++) ls[j] = i0 + j < nlist ? (has_perm ? (int)pw[j] : i0 + j) : -1;
+}
+
+// Count, then this: every work group loads all nlist counts, the item order
+// and the lists' geometry next to its entries (one round trip, every load in
+// flight at once), scans the counts in LDS (bf_offsets) and fills PER entries
+// per thread and round from LDS alone.  Work group 0 writes the global offset
+// arrays.
+//
+// Clearing the counts for the next call (a replayed graph relies on it, so
+// the buffers cannot alternate): each group draws a ticket once its counts
+// are in LDS; the group that draws the last one stores the zeros and resets
+// the ticket.  No group waits for another, and within a group only the first
+// wave, after its own fill, waits for the atomic to return.  The zeros need
+// no inter-group release / acquire: a group's count loads have returned
+// before its ticket is drawn (their values are in LDS before the barriers
+// the draw follows), the zeros are stored only after the last draw has
+// returned, and the last group reads nothing another group wrote in this
+// launch — the zeros and the ticket are read by the next launch only, across
+// a kernel boundary like every other store here.
+template <int E, int PER>
+__global__ __launch_bounds__(1024) void k_bucket_fill_scan(BFArgs a, uint32_t* counts,
+                                                           const uint32_t* __restrict__ pos,
+                                                           uint32_t* ticket) {
+    extern __shared__ uint32_t bf_lds[];  // cnt[nlist], off[nlist], geo[nlist] {len, offset}
+    __shared__ uint32_t wb[16], wi[16], s_last;
+    uint32_t* cnt = bf_lds;
+    uint32_t* off = bf_lds + a.nlist;
+    uint2* geo = (uint2*)(bf_lds + 2 * a.nlist);
+    const int t = threadIdx.x, l0 = E * t;
+    const int qs = (a.QT & (a.QT - 1)) == 0 ? __builtin_ctz((unsigned)a.QT) : -1;
+    uint32_t c[E], pw[E], gl[E], go[E];
+    int ls[E], el[PER];
+    uint32_t ep[PER];
+    bf_load_words<E>(counts, a.nlist, c);
+    bf_load_words<E>(a.perm ? a.perm : counts, a.nlist, pw);
+    bf_load_words<E>(a.list_len, a.nlist, gl);
+    bf_load_words<E>(a.list_off, a.nlist, go);
+    // (the slot of an entry that was not counted is stale; bf_store ignores it)
+    auto load = [&](int64_t base) {
+#pragma unroll
+        for (int j = 0; j < PER; j++) {
+            const int64_t e = min(base + (int64_t)j * 1024 + t, a.total - 1);
+            el[j] = a.assign[e];
+            ep[j] = pos[e];
+        }
+        // both words are looked at here, so they are waited for here, ahead of
+        // the stores: a wait placed among the stores would wait for those too
+#pragma unroll
+        for (int j = 0; j < PER; j++) {
+            const bool in = el[j] >= 0 && el[j] < a.nlist;
+            el[j] = in ? el[j] : -1;
+            ep[j] = in ? ep[j] : 0u;
+        }
+    };
+    int64_t base = (int64_t)blockIdx.x * 1024 * PER;
+    load(base);
+#pragma unroll
+    for (int j = 0; j < E; j++) {
+        if (l0 + j < a.nlist) {
+            cnt[l0 + j] = c[j];
+            geo[l0 + j] = make_uint2(gl[j], go[j]);
+        } else {
+            c[j] = 0u;
+        }
+    }
+    bf_item_order<E>(a.perm != nullptr, a.nlist, pw, ls);
+    __syncthreads();
+    // The draw: issued here, looked at after the fill, so that nothing waits
+    // for the atomic's round trip.  tk is thread 0's alone (no value on the
+    // other path, so no copy that would wait for it where the branch ends),
+    // and the zero from a register the compiler cannot see through keeps the
+    // address from counting as uniform: for a uniform address the compiler
+    // folds the wave's lanes into one atomic and reads its result back at once.
+    uint32_t tk, zero;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
+    if (t == 0)
+        tk = __hip_atomic_fetch_add(ticket + zero, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    bf_offsets<E>(a, cnt, off, wb, wi, c, ls, qs, blockIdx.x == 0);
+    for (;;) {
+#pragma unroll
+        for (int j = 0; j < PER; j++) {
+            const int64_t e = base + (int64_t)j * 1024 + t;
+            if (e < a.total) bf_store(a, cnt, off, geo, qs, e, el[j], ep[j]);
+        }
+        base += (int64_t)gridDim.x * 1024 * PER;
+        if (base >= a.total) break;
+        load(base);
+    }
+    if (t == 0) s_last = tk == gridDim.x - 1u ? 1u : 0u;
+    __syncthreads();
+    if (s_last) {  // clear where the draw was the last
+        const int n4 = a.nlist & ~3;
+        for (int i = 4 * t; i < n4; i += 4096) *(uint4*)(counts + i) = make_uint4(0u, 0u, 0u, 0u);
+        if (t < 4 && n4 + t < a.nlist) counts[n4 + t] = 0u;
+        if (t == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// One work group for the whole stage (at most 1024 PER entries): the LDS
+// histogram of k_bucket_count_lds with the slots kept in registers, the scan,
+// the fill.  The global counts and the slot array are not touched.  The
+// lists' geometry goes through LDS here too (loaded beside the entries), so
+// the histogram follows one round trip to memory instead of a gather of the
+// list lengths after the assignment's.
+template <int E, int PER>
+__global__ __launch_bounds__(1024) void k_bucket_one(BFArgs a) {
+    extern __shared__ uint32_t bf_lds[];  // cnt[nlist], off[nlist], geo[nlist] {len, offset}
+    __shared__ uint32_t wb[16], wi[16];
+    uint32_t* cnt = bf_lds;
+    uint32_t* off = bf_lds + a.nlist;
+    uint2* geo = (uint2*)(bf_lds + 2 * a.nlist);
+    const int t = threadIdx.x, l0 = E * t;
+    const int qs = (a.QT & (a.QT - 1)) == 0 ? __builtin_ctz((unsigned)a.QT) : -1;
+    uint32_t pw[E], gl[E], go[E], ep[PER];
+    int ls[E], el[PER];
+#pragma unroll
+    for (int j = 0; j < PER; j++)
+        el[j] = a.assign[min((int64_t)j * 1024 + t, a.total - 1)];
+    bf_load_words<E>(a.perm ? a.perm : a.list_len, a.nlist, pw);
+    bf_load_words<E>(a.list_len, a.nlist, gl);
+    bf_load_words<E>(a.list_off, a.nlist, go);
+#pragma unroll
+    for (int j = 0; j < E; j++) {
+        if (l0 + j < a.nlist) {
+            cnt[l0 + j] = 0u;
+            geo[l0 + j] = make_uint2(gl[j], go[j]);
+        }
+    }
+    bf_item_order<E>(a.perm != nullptr, a.nlist, pw, ls);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < PER; j++) {
+        const int l = el[j];
+        // an empty list is no list, nor is what lies past the batch
+        const bool ok = (int64_t)j * 1024 + t < a.total && l >= 0 && l < a.nlist && geo[l].x > 0u;
+        el[j] = ok ? l : -1;
+        ep[j] = ok ? atomicAdd(&cnt[l], 1u) : 0u;
+    }
+    __syncthreads();
+    uint32_t c[E];
+#pragma unroll
+    for (int j = 0; j < E; j++) c[j] = l0 + j < a.nlist ? cnt[l0 + j] : 0u;
+    bf_offsets<E>(a, cnt, off, wb, wi, c, ls, qs, true);
+#pragma unroll
+    for (int j = 0; j < PER; j++) {
+        const int64_t e = (int64_t)j * 1024 + t;
+        if (e < a.total) bf_store(a, cnt, off, geo, qs, e, el[j], ep[j]);
+    }
+}
+
 __global__ void k_stamp(unsigned long long* out) { *out = __builtin_amdgcn_s_memrealtime(); }
 void device_stamp(unsigned long long* out, hipStream_t s) {
     k_stamp<<<dim3(1), dim3(1), 0, s>>>(out);
@@ -517,10 +859,57 @@ void probe_limits(const int32_t* assign, int64_t n, int nprobe, const uint32_t* 
     HIP_LAUNCH_CHECK();
 }
 
+namespace {
+// the LDS of the scan inside the fill, four words per list (count, offset,
+// length, arena offset): past 64 KB with the static words (4096 lists; 128 KB
+// at 8192) the dynamic limit is raised, as for k_bucket_count_lds
+template <class K>
+size_t bf_lds_bytes(K kernel, int nlist) {
+    const size_t lds = sizeof(uint32_t) * 4 * (size_t)nlist;
+    if (lds + 1024 > 65536)
+        HIP_CHECK(hipFuncSetAttribute((const void*)kernel,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return lds;
+}
+template <int E, int PER>
+void bucket_fill_scan(const BFArgs& a, const IVFBuckets& b, hipStream_t s) {
+    // at most 512 work groups, each looping over its rounds of entries
+    const int64_t groups = std::min<int64_t>(cdiv(a.total, 1024 * PER), 512);
+    const size_t lds = bf_lds_bytes(k_bucket_fill_scan<E, PER>, a.nlist);
+    k_bucket_fill_scan<E, PER><<<dim3((unsigned)groups), dim3(1024), lds, s>>>(a, b.counts, b.cursor,
+                                                                             b.ticket);
+}
+template <int E, int PER>
+void bucket_one(const BFArgs& a, hipStream_t s) {
+    const size_t lds = bf_lds_bytes(k_bucket_one<E, PER>, a.nlist);
+    k_bucket_one<E, PER><<<dim3(1), dim3(1024), lds, s>>>(a);
+}
+}  // namespace
+
 void ivf_bucket(const int32_t* assign, int64_t n, int nprobe, const uint32_t* list_len,
                 const uint32_t* list_off, int nlist, int QT, IVFBuckets b, hipStream_t s) {
     int64_t total = n * nprobe;
     FAISS_THROW_IF_NOT_MSG(total < (1ll << 32), "n * nprobe must fit in 32 bits");
+    // up to BF_MAXL lists the fill scans the counts itself (no scan launch)
+    const bool fused = total > 0 && nlist <= BF_MAXL && !b.item_list;
+    const BFArgs fa{assign,     total,      list_len,  list_off,  nlist,          QT,
+                    b.bucket_off, b.item_off, b.item_ctr, b.perm,    b.entries,      b.item_entries,
+                    b.item_desc, b.mark_keys, b.mark_recs, b.mark_ke};
+    if (fused && total <= BF_ONE_MAX) {
+        // one work group, one launch; the counts stay zero and unread
+        const int64_t per = (int64_t)cdiv(total, 1024);
+        if (nlist <= 4096) {
+            if (per <= 4) bucket_one<4, 4>(fa, s);
+            else if (per <= 8) bucket_one<4, 8>(fa, s);
+            else bucket_one<4, 16>(fa, s);
+        } else {
+            if (per <= 4) bucket_one<8, 4>(fa, s);
+            else if (per <= 8) bucket_one<8, 8>(fa, s);
+            else bucket_one<8, 16>(fa, s);
+        }
+        HIP_LAUNCH_CHECK();
+        return;
+    }
     if (!b.counts_next) HIP_CHECK(hipMemsetAsync(b.counts, 0, sizeof(uint32_t) * nlist, s));
     if (total > 0) {
         // entries per thread: enough work groups to spread the histogram
@@ -555,6 +944,22 @@ void ivf_bucket(const int32_t* assign, int64_t n, int nprobe, const uint32_t* li
 #undef BCL
         HIP_LAUNCH_CHECK();
         }
+    }
+    // the fill scans the counts and the group with the last ticket clears
+    // them (the self-cleaning counts of every caller; else the old kernels).
+    // Two entries per thread while that gives every CU at most one work
+    // group, else four.
+    if (fused && b.ticket && b.counts_next == b.counts) {
+        const bool two = cdiv(total, 2048) <= 256;
+        if (nlist <= 4096) {
+            if (two) bucket_fill_scan<4, 2>(fa, b, s);
+            else bucket_fill_scan<4, 4>(fa, b, s);
+        } else {
+            if (two) bucket_fill_scan<8, 2>(fa, b, s);
+            else bucket_fill_scan<8, 4>(fa, b, s);
+        }
+        HIP_LAUNCH_CHECK();
+        return;
     }
     // beyond 8192 lists (and up to 64 groups of 4096): the scan over many
     // work groups, its block totals after the work counter (b.scan_tmp);
