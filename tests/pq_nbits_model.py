@@ -21,6 +21,8 @@
   dis > radius (inner product), in arrival order.
 
 fp32 throughout; fma() is correctly rounded (round-to-odd in float64)."""
+import bisect
+
 import numpy as np
 
 F32 = np.float32
@@ -119,6 +121,30 @@ def ref_dist(x, Y, l2):
     return r
 
 
+def heap_topk(arrivals, k, l2):
+    """The reference's result heap over (distance, id) pairs in arrival order:
+    a row is admitted when its distance strictly beats the heap's top (FLT_MAX /
+    -FLT_MAX while the heap is not full), the worst (distance, id) pair is
+    evicted, and the pairs come out best first, padded with -1 and +-FLT_MAX.
+    Returns (D [k], I [k])."""
+    D = np.full(k, FLT_MAX if l2 else -FLT_MAX, F32)
+    I = np.full(k, -1, np.int64)
+    heap = []  # best first; the last entry is the heap's top
+    for dis, i in arrivals:
+        key = (dis, i) if l2 else (-dis, -i)
+        if len(heap) < k:
+            if not (dis < FLT_MAX if l2 else dis > -FLT_MAX):
+                continue
+        elif key[0] < heap[-1][0]:  # strict admission on the distance alone
+            heap.pop()
+        else:
+            continue
+        bisect.insort(heap, key)
+    for j, (a, b) in enumerate(heap):
+        D[j], I[j] = (a, b) if l2 else (-a, -b)
+    return D, I
+
+
 class Model:
     """An IVF-PQ index as arrays: coarse centroids [nlist, d], PQ centroids
     [M, ksub, dsub], per list its packed codes [len, code_size] and ids."""
@@ -202,24 +228,11 @@ class Model:
 
     def search_preassigned(self, xq, k, keys, cdis, sel=None, max_codes=0):
         nq = len(xq)
-        D = np.full((nq, k), FLT_MAX if self.l2 else -FLT_MAX, F32)
-        I = np.full((nq, k), -1, np.int64)
+        D = np.empty((nq, k), F32)
+        I = np.empty((nq, k), np.int64)
         for q in range(nq):
             cd = cdis[q] if cdis is not None else None
-            heap = []  # best first; the last entry is the heap's top
-            for dis, i in self.arrivals(xq[q], keys[q], cd, sel, max_codes):
-                key = (dis, i) if self.l2 else (-dis, -i)
-                if len(heap) < k:
-                    if not (dis < FLT_MAX if self.l2 else dis > -FLT_MAX):
-                        continue
-                elif key[0] < heap[-1][0]:  # strict admission on the distance alone
-                    heap.pop()
-                else:
-                    continue
-                heap.append(key)
-                heap.sort()
-            for j, (a, b) in enumerate(heap):
-                D[q, j], I[q, j] = (a, b) if self.l2 else (-a, -b)
+            D[q], I[q] = heap_topk(self.arrivals(xq[q], keys[q], cd, sel, max_codes), k, self.l2)
         return D, I
 
     def range_search_preassigned(self, xq, radius, keys, cdis):
