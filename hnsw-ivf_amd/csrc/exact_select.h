@@ -225,5 +225,101 @@ __device__ __forceinline__ bool exact_topk_small(float (&k1)[NB], long long (&k2
     return true;
 }
 
+// The boundary tie exact_topk_small declines, resolved where the keys are:
+// the same candidates (64 b + lane < ns holds (k1[b], k2[b]), padding and
+// inadmissible ones +inf / WS_NOID) with their arrival ranks ar[b] (distinct
+// among the candidates; what the Stream's for_each would pass as `rank`), and
+// the result of exact_topk_resolve over that stream, without walking it again:
+//   v    = the k-th smallest k1 (finite: the caller saw a tie at the boundary),
+//   S    = the first k arrivals among the candidates with k1 <= v,
+//   out  = the a keys < v in (k1, k2) order, then the k - a tied members of S
+//          with the smallest k2, ascending.
+// Two broadcast loops over the candidates (the second over the tied members
+// of S only); a resolve costs three or four walks of the stream, each with its
+// exact distances recomputed.
+template <int NB, class OutIdx = int64_t>
+__device__ __forceinline__ void exact_topk_tied_small(const float (&k1)[NB],
+                                                      const long long (&k2)[NB],
+                                                      const long long (&ar)[NB], int ns, int k,
+                                                      int metric_l2, int lane, bool write,
+                                                      float* __restrict__ Dq,
+                                                      OutIdx* __restrict__ Iq) {
+    const float v = wave_kth_smallest<NB>(k1, k);  // exact (LOWB = 0)
+    int lex[NB], arr[NB];
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        lex[b] = 0;
+        arr[b] = 0;
+    }
+    // lex: candidates before this one by (k1, k2, position); arr: candidates
+    // with k1 <= v that arrived before it
+#pragma unroll
+    for (int bb = 0; bb < NB; bb++) {
+        const int nj = min(64, ns - 64 * bb);
+        for (int j = 0; j < nj; j++) {
+            const float a1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(k1[bb]), j));
+            const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)(k2[bb] & 0xffffffffLL), j);
+            const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(k2[bb] >> 32), j);
+            const long long a2 = (long long)(((unsigned long long)hi << 32) | lo);
+            const uint32_t rlo = __builtin_amdgcn_readlane((uint32_t)(ar[bb] & 0xffffffffLL), j);
+            const uint32_t rhi = __builtin_amdgcn_readlane((uint32_t)(ar[bb] >> 32), j);
+            const long long ra = (long long)(((unsigned long long)rhi << 32) | rlo);
+            const bool in = a1 <= v;  // wave-uniform
+            const int pj = 64 * bb + j;
+#pragma unroll
+            for (int b = 0; b < NB; b++) {
+                if (64 * b < ns) {
+                    const bool before =
+                            a1 < k1[b] ||
+                            (a1 == k1[b] && (a2 < k2[b] || (a2 == k2[b] && pj < 64 * b + lane)));
+                    lex[b] += before ? 1 : 0;
+                    arr[b] += in && ra < ar[b] ? 1 : 0;
+                }
+            }
+        }
+    }
+    int a = 0, r2[NB];
+    unsigned long long tied[NB];  // the tied members of S (wave-uniform masks)
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const bool cand = 64 * b + lane < ns;
+        a += __popcll(__ballot(cand && k1[b] < v));
+        tied[b] = __ballot(cand && k1[b] == v && arr[b] < k);
+        r2[b] = 0;
+    }
+    // r2: tied members of S before this one by (k2, position)
+#pragma unroll
+    for (int bb = 0; bb < NB; bb++) {
+        unsigned long long m = tied[bb];
+        while (m) {
+            const int j = __ffsll((long long)m) - 1;
+            m &= m - 1ull;
+            const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)(k2[bb] & 0xffffffffLL), j);
+            const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(k2[bb] >> 32), j);
+            const long long a2 = (long long)(((unsigned long long)hi << 32) | lo);
+            const int pj = 64 * bb + j;
+#pragma unroll
+            for (int b = 0; b < NB; b++)
+                r2[b] += a2 < k2[b] || (a2 == k2[b] && pj < 64 * b + lane) ? 1 : 0;
+        }
+    }
+    if (write) {
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            if (64 * b + lane >= ns) continue;
+            int slot = -1;
+            if (k1[b] < v) slot = lex[b];
+            else if (((tied[b] >> lane) & 1ull) && a + r2[b] < k) slot = a + r2[b];
+            if (slot >= 0) {
+                float dis;
+                long long id;
+                from_key(metric_l2, k1[b], k2[b], dis, id);
+                Dq[slot] = dis;
+                Iq[slot] = (OutIdx)id;
+            }
+        }
+    }
+}
+
 }  // namespace kern
 }  // namespace faiss_amd

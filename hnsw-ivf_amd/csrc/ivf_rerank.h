@@ -281,6 +281,7 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
     __shared__ __attribute__((aligned(16))) float xsh[RR_W][BDM];
     // scratch of the small-batch compaction (64 NB keys + labels, NB <= 4)
     __shared__ __attribute__((aligned(16))) float stg[RR_W][64 * 4 * 3];
+    __shared__ uint16_t cpos[RR_W][256];  // candidate numbers of the compacted keys (ties)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t q0 = (int64_t)blockIdx.x * RR_W + w;
     const bool valid = q0 < n;
@@ -460,6 +461,12 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
     // directly, anything else goes through the general resolve
     bool done = false;
     unsigned long long t_e = 0ull;
+    // arrival rank of candidate c of the list (probe rank, then arena row: the
+    // order the reference scans in), for a boundary tie resolved on the keys
+    // at hand (exact_topk_tied_small)
+    auto arank = [&](int c) {
+        return ((long long)sprobe[w][c] << 32) | (long long)surv[w][c];
+    };
     auto small = [&](auto nbc) {
         constexpr int NB = decltype(nbc)::value;
         if constexpr (NB == 1) {
@@ -473,8 +480,13 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
                 k2[0] = WS_NOID;
             }
             t_e = trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
-            return exact_topk_small<1>(k1, k2, ns, k, L2 ? 1 : 0, lane, valid, D + q * k,
-                                       I + q * k);
+            if (!exact_topk_small<1>(k1, k2, ns, k, L2 ? 1 : 0, lane, valid, D + q * k,
+                                     I + q * k)) {
+                const long long ar[1] = {ok ? arank(lane) : 0ll};
+                exact_topk_tied_small<1>(k1, k2, ar, ns, k, L2 ? 1 : 0, lane, valid, D + q * k,
+                                         I + q * k);
+            }
+            return true;
         } else {
             // only keys <= U can be in the top k (at least k kept entries have
             // exact keys <= their ub' <= U; boundary ties are <= U too): each
@@ -498,6 +510,7 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
                 if (in) {
                     ck1[pos] = a1;
                     ck2[pos] = a2;
+                    cpos[w][pos] = (uint16_t)(64 * b + lane);
                 }
                 m += __popcll(bm);
             }
@@ -506,8 +519,13 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
             if (m <= 64) {
                 float c1[1] = {lane < m ? ck1[lane] : WS_INF};
                 long long c2[1] = {lane < m ? ck2[lane] : WS_NOID};
-                return exact_topk_small<1>(c1, c2, m, k, L2 ? 1 : 0, lane, valid, D + q * k,
-                                           I + q * k);
+                if (!exact_topk_small<1>(c1, c2, m, k, L2 ? 1 : 0, lane, valid, D + q * k,
+                                         I + q * k)) {
+                    const long long ar[1] = {lane < m ? arank((int)cpos[w][lane]) : 0ll};
+                    exact_topk_tied_small<1>(c1, c2, ar, m, k, L2 ? 1 : 0, lane, valid,
+                                             D + q * k, I + q * k);
+                }
+                return true;
             }
             float k1[NB];
             long long k2[NB];
@@ -517,8 +535,16 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
                 k1[b] = has ? ck1[64 * b + lane] : WS_INF;
                 k2[b] = has ? ck2[64 * b + lane] : WS_NOID;
             }
-            return exact_topk_small<NB>(k1, k2, m, k, L2 ? 1 : 0, lane, valid, D + q * k,
-                                        I + q * k);
+            if (!exact_topk_small<NB>(k1, k2, m, k, L2 ? 1 : 0, lane, valid, D + q * k,
+                                      I + q * k)) {
+                long long ar[NB];
+#pragma unroll
+                for (int b = 0; b < NB; b++)
+                    ar[b] = 64 * b + lane < m ? arank((int)cpos[w][64 * b + lane]) : 0ll;
+                exact_topk_tied_small<NB>(k1, k2, ar, m, k, L2 ? 1 : 0, lane, valid, D + q * k,
+                                          I + q * k);
+            }
+            return true;
         }
     };
     // ---- Flat, common path (no failing stream, P < ns <= RR2_CAP): two
@@ -531,8 +557,8 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
     // The window above the k-th approximation shrinks from 2 M to about M
     // (c2: 34.8 -> 22.3 rows per query).  With fewer than k admissible
     // keys in A every candidate is evaluated.  The A u B keys are ranked as
-    // the single sweep's are; a boundary tie goes to exact_topk_resolve over
-    // the whole candidate list (surv[] is left as it was).
+    // the single sweep's are; a boundary tie is resolved on them by arrival
+    // rank (surv[] / sprobe[] are left as they were).
     int nrows = min(ns, RR_CAP);  // rows evaluated exactly (stats, trace)
     unsigned long long t_a = 0ull;
     auto two_round = [&](auto nbc, int P) {
@@ -617,15 +643,33 @@ __global__ __launch_bounds__(64 * RR_W, RR_WAVES) void k_ivf_rerank(
                 k2[b] = sa2[j - nb];
             }
         }
+        // (position j of the A u B order: B's candidates, then A's; the
+        // candidates left out have lb' > T >= the k-th key and take no part in
+        // a tie)
+        auto arank2 = [&](int j) {
+            return j < m ? arank(j < nb ? (int)ordb[j] : (int)orda[j - nb]) : 0ll;
+        };
         if constexpr (NB > 1) {
             if (m <= 64) {
                 float c1[1] = {k1[0]};
                 long long c2[1] = {k2[0]};
-                return exact_topk_small<1>(c1, c2, m, k, L2 ? 1 : 0, lane, valid, D + q * k,
-                                           I + q * k);
+                if (!exact_topk_small<1>(c1, c2, m, k, L2 ? 1 : 0, lane, valid, D + q * k,
+                                         I + q * k)) {
+                    const long long ar[1] = {arank2(lane)};
+                    exact_topk_tied_small<1>(c1, c2, ar, m, k, L2 ? 1 : 0, lane, valid,
+                                             D + q * k, I + q * k);
+                }
+                return true;
             }
         }
-        return exact_topk_small<NB>(k1, k2, m, k, L2 ? 1 : 0, lane, valid, D + q * k, I + q * k);
+        if (!exact_topk_small<NB>(k1, k2, m, k, L2 ? 1 : 0, lane, valid, D + q * k, I + q * k)) {
+            long long ar[NB];
+#pragma unroll
+            for (int b = 0; b < NB; b++) ar[b] = arank2(64 * b + lane);
+            exact_topk_tied_small<NB>(k1, k2, ar, m, k, L2 ? 1 : 0, lane, valid, D + q * k,
+                                      I + q * k);
+        }
+        return true;
     };
     bool two = false;
     if constexpr (PQD == 0) {

@@ -701,7 +701,8 @@ struct CoarseStream {
 // the streams' dropped bounds and the query; U = k-th smallest ub' = approx_hi
 // + M; candidates = entries with approx_lo - M <= U of the streams that did
 // not fail, plus every centroid of the failing streams; exact evaluation and a
-// rank-based top-k (exact_topk_resolve when a tie crosses the boundary).
+// rank-based top-k (a tie across the boundary: exact_topk_tied_small on the
+// same keys; exact_topk_resolve for more than 256 candidates).
 template <bool L2, class OutIdx, int V>
 #ifndef CR_WAVES
 #define CR_WAVES 4  // waves per SIMD the re-rank is compiled for (tuning)
@@ -875,12 +876,26 @@ __global__ __launch_bounds__(64, CR_WAVES) void k_coarse_rerank(
                 float c1[1] = {lane < m ? ck1[lane] : WS_INF};
                 long long c2[1] = {lane < m ? ck2[lane] : WS_NOID};
                 __syncthreads();
-                return exact_topk_small<1, OutIdx>(c1, c2, m, k, L2 ? 1 : 0, lane, valid,
-                                                   D + q * k, I + q * k);
+                if (!exact_topk_small<1, OutIdx>(c1, c2, m, k, L2 ? 1 : 0, lane, valid,
+                                                 D + q * k, I + q * k)) {
+                    const long long ar[1] = {L2 ? c2[0] : -c2[0]};
+                    exact_topk_tied_small<1, OutIdx>(c1, c2, ar, m, k, L2 ? 1 : 0, lane, valid,
+                                                     D + q * k, I + q * k);
+                }
+                return true;
             }
         }
-        return exact_topk_small<NB, OutIdx>(k1, k2, ns, k, L2 ? 1 : 0, lane, valid, D + q * k,
-                                            I + q * k);
+        // a boundary tie is resolved on the keys at hand (arrival order = the
+        // centroid number, which the key's second word carries)
+        if (!exact_topk_small<NB, OutIdx>(k1, k2, ns, k, L2 ? 1 : 0, lane, valid, D + q * k,
+                                          I + q * k)) {
+            long long ar[NB];
+#pragma unroll
+            for (int b = 0; b < NB; b++) ar[b] = L2 ? k2[b] : -k2[b];
+            exact_topk_tied_small<NB, OutIdx>(k1, k2, ar, ns, k, L2 ? 1 : 0, lane, valid,
+                                              D + q * k, I + q * k);
+        }
+        return true;
     };
     if (ns <= 64) done = small(std::integral_constant<int, 1>());
     else if (ns <= 128) done = small(std::integral_constant<int, 2>());
