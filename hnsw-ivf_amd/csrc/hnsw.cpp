@@ -61,6 +61,25 @@ inline float l2_seq(const float* a, const float* b, int d) {
     return r;
 }
 
+// fvec_inner_product in the same order (ref_arith.h: the term is x * y)
+inline float ip_seq(const float* a, const float* b, int d) {
+    float c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int n8 = d & ~7;
+    for (int i = 0; i < n8; i += 8)
+        for (int j = 0; j < 8; j++) c[j] = std::fma(a[i + j], b[i + j], c[j]);
+    const float x0 = c[0] + c[4], x1 = c[1] + c[5], x2 = c[2] + c[6], x3 = c[3] + c[7];
+    float r = (x0 + x2) + (x1 + x3);
+    int i = n8;
+    if (d - n8 >= 4) {
+        float e[4];
+        for (int j = 0; j < 4; j++) e[j] = a[n8 + j] * b[n8 + j];
+        r = r + ((e[0] + e[2]) + (e[1] + e[3]));
+        i += 4;
+    }
+    for (; i < d; i++) r = std::fma(a[i], b[i], r);
+    return r;
+}
+
 struct NodeDistCloser {  // faiss/impl/HNSW.h NodeDistCloser
     float d;
     int id;
@@ -78,10 +97,15 @@ struct Builder {
     HNSW& h;
     const float* xb;
     int d;
+    bool ip;  // inner product: NegativeDistanceComputer over FlatIPDis (faiss/IndexHNSW.cpp:60-65)
     std::vector<uint8_t> visited;
-    Builder(HNSW& h_, const float* xb_, int d_, size_t n) : h(h_), xb(xb_), d(d_), visited(n, 0) {}
-    float dis(const float* q, int id) const { return l2_seq(q, xb + (size_t)id * d, d); }
-    float sym(int a, int b) const { return l2_seq(xb + (size_t)a * d, xb + (size_t)b * d, d); }
+    Builder(HNSW& h_, const float* xb_, int d_, size_t n, bool ip_)
+            : h(h_), xb(xb_), d(d_), ip(ip_), visited(n, 0) {}
+    float dis2(const float* a, const float* b) const {
+        return ip ? -ip_seq(a, b, d) : l2_seq(a, b, d);
+    }
+    float dis(const float* q, int id) const { return dis2(q, xb + (size_t)id * d); }
+    float sym(int a, int b) const { return dis2(xb + (size_t)a * d, xb + (size_t)b * d); }
 
     void greedy(const float* q, int level, int& nearest, float& d_nearest) {
         for (;;) {
@@ -228,7 +252,10 @@ void HNSW::set_default_probas(int M, float levelMult) {
     int nn = 0;
     cum_nneighbor_per_level.push_back(0);
     for (int level = 0;; level++) {
-        float proba = expf(-level / levelMult) * (1 - expf(-1 / levelMult));
+        // (the reference's exp is the double one: faiss/impl/HNSW.cpp:88; the
+        // index file carries these values)
+        float proba = (float)(std::exp((double)(-level / levelMult)) *
+                              (1 - std::exp((double)(-1 / levelMult))));
         if (proba < 1e-9) break;
         assign_probas.push_back(proba);
         nn += level == 0 ? M * 2 : M;
@@ -270,7 +297,6 @@ IndexHNSW::~IndexHNSW() {
 IndexHNSWFlat::IndexHNSWFlat(int d_, int M, MetricType metric)
         : IndexHNSW(new IndexFlat(d_, metric), M) {
     own_fields = true;
-    FAISS_THROW_IF_NOT_MSG(metric == METRIC_L2, "HNSW inner product not supported on GPU");
 }
 
 void IndexHNSW::add(idx_t n, const float* x) {
@@ -309,7 +335,7 @@ void IndexHNSW::add(idx_t n, const float* x) {
         order[offs[pl]++] = (int)(n0 + i);
     }
     std::mt19937 rng2(789);
-    Builder bld(hnsw, storage->xb.data(), d, ntotal);
+    Builder bld(hnsw, storage->xb.data(), d, ntotal, metric_type == METRIC_INNER_PRODUCT);
     int i1 = (int)n;
     for (int pl = (int)hist.size() - 1; pl >= 0; pl--) {
         int i0 = i1 - hist[pl];
@@ -474,6 +500,7 @@ void IndexHNSW::hnsw_device(idx_t n, const float* x, int ldx, int k, float* dist
     kern::HNSWMode mode;
     mode.check_relative_distance = sm.check_relative_distance;
     mode.bounded_queue = sm.bounded_queue;
+    mode.inner_product = metric_type == METRIC_INNER_PRODUCT;
     if (sm.sel && ntotal > 0) {
         // the selector over the nodes 0 .. ntotal - 1 (the storage's rows),
         // one byte each, in s_rlog_: a selector keeps the register kernel,

@@ -441,7 +441,15 @@ struct HNSWMode {
     bool check_relative_distance = true;
     bool bounded_queue = true;
     const uint8_t* mask = nullptr;  // [ntotal] 1 = member; null: every node
-    bool is_default() const { return check_relative_distance && bounded_queue && !mask; }
+    // METRIC_INNER_PRODUCT: the distance is -<q, y> (the reference's
+    // NegativeDistanceComputer, faiss/IndexHNSW.cpp:60-65) and the outputs are
+    // negated back.  Served by the sequential kernels alone (k_hnsw_exact,
+    // k_hnsw_unbounded, k_hnsw_exact_reg without the int8 image and the replay
+    // log): the other kernels' prefilter and tie flagging assume L2.
+    bool inner_product = false;
+    // the level-0 search in its default form (as opposed to the EXT forms)
+    bool default_level0() const { return check_relative_distance && bounded_queue && !mask; }
+    bool is_default() const { return default_level0() && !inner_product; }
 };
 // reference faiss/impl/HNSW.cpp:943-996 (HNSW::search), :852-924 (greedy),
 // :605-741 (search_from_candidates), :1096-1342 (MinimaxHeap)

@@ -43,6 +43,20 @@ __device__ __forceinline__ float l2_row(const float* __restrict__ qs, const floa
                                         int d) {
     return ref_l2(qs, y, d);
 }
+// METRIC_INNER_PRODUCT: faiss FlatIPDis (faiss/IndexFlat.cpp:176-240) under
+// NegativeDistanceComputer (faiss/impl/DistanceComputer.h:65-110): the
+// rounded fvec_inner_product with its sign flipped
+// (a NaN stays the positive quiet NaN an L2 distance would be, whatever its
+// sign: above FLT_MAX in the kernels' key order, it never enters the results)
+__device__ __forceinline__ float neg_ip(float ip) {
+    return ip != ip ? __int_as_float(0x7fc00000) : -ip;
+}
+template <bool IP>
+__device__ __forceinline__ float hnsw_row(const float* __restrict__ qs, const float* __restrict__ y,
+                                          int d) {
+    if (IP) return neg_ip(ref_ip(qs, y, d));
+    return l2_row(qs, y, d);
+}
 
 // merge a sorted 64-batch into a sorted 128-queue (c0: positions 0..63,
 // c1: 64..127), keeping the 128 smallest.
@@ -402,10 +416,21 @@ struct ArrivalLog {
     int64_t slots = 0;
     int64_t cap = 0;
 };
+// (IP: the signed distance -<q, y> through the order-preserving map of its
+// bits — negative: all bits flipped, else the sign bit set — so the keys
+// order as unsigned for both metrics)
+template <bool IP = false>
 __device__ __forceinline__ uint64_t sx_key(float d, int32_t id) {
-    return ((uint64_t)(uint32_t)__float_as_int(d) << 32) | (uint32_t)(id ^ (int32_t)0x80000000);
+    uint32_t b = (uint32_t)__float_as_int(d);
+    if (IP) b ^= (uint32_t)((int32_t)b >> 31) | 0x80000000u;
+    return ((uint64_t)b << 32) | (uint32_t)(id ^ (int32_t)0x80000000);
 }
-__device__ __forceinline__ float sx_dis(uint64_t k) { return __int_as_float((int)(k >> 32)); }
+template <bool IP = false>
+__device__ __forceinline__ float sx_dis(uint64_t k) {
+    uint32_t b = (uint32_t)(k >> 32);
+    if (IP) b ^= (uint32_t)((int32_t)~b >> 31) | 0x80000000u;
+    return __int_as_float((int)b);
+}
 __device__ __forceinline__ int32_t sx_id(uint64_t k) { return (int32_t)((uint32_t)k ^ 0x80000000u); }
 __host__ __device__ inline int seq_qpad(int ld) { return ld < 128 ? 128 : ld; }
 // slots of a heap of capacity c (1-based, index 0 unused, sibling pairs
@@ -460,10 +485,11 @@ __device__ __forceinline__ void sx_push(uint64_t* b, int n, uint64_t val, int la
 
 // greedy descent over the levels above 0 (HNSW.cpp:852-924), as in
 // k_hnsw_search: from the entry point to level 0's seed (nearest, d_nearest)
+template <bool IP>
 __device__ __forceinline__ void seq_greedy(const HNSWDevice& g, const float* qs, int lane,
                                            int& nearest, float& d_nearest, uint32_t& st_ndis,
                                            uint32_t& st_nhops) {
-    d_nearest = l2_row(qs, g.storage + (int64_t)nearest * g.ld, g.d);
+    d_nearest = hnsw_row<IP>(qs, g.storage + (int64_t)nearest * g.ld, g.d);
     for (int level = g.max_level; level >= 1; level--) {
         for (;;) {
             const uint64_t o = g.offsets[nearest];
@@ -474,7 +500,7 @@ __device__ __forceinline__ void seq_greedy(const HNSWDevice& g, const float* qs,
                     __ballot(lane < cnt && v < 0) | (cnt < 64 ? (~0ull << cnt) : 0ull);
             const int first_neg = neg ? __ffsll((long long)neg) - 1 : 64;
             float dis = WS_INF;
-            if (lane < first_neg) dis = l2_row(qs, g.storage + (int64_t)v * g.ld, g.d);
+            if (lane < first_neg) dis = hnsw_row<IP>(qs, g.storage + (int64_t)v * g.ld, g.d);
             st_ndis += (uint32_t)min(first_neg, 64);
             st_nhops += 1;
             float md = dis;
@@ -504,6 +530,7 @@ __device__ __forceinline__ void seq_greedy(const HNSWDevice& g, const float* qs,
 // same node; the fresh ones keep their stored order).  Lane t < nf returns
 // the t-th fresh node (fv) and its distance (fdis), 4 lanes per row in the
 // reference order for d <= 128.
+template <bool IP>
 __device__ __forceinline__ int seq_fresh_rows(const HNSWDevice& g, const float* qs, uint32_t* vis,
                                               int32_t v0, int cnt, int lane, int32_t& fv,
                                               float& fdis) {
@@ -532,10 +559,11 @@ __device__ __forceinline__ int seq_fresh_rows(const HNSWDevice& g, const float* 
     // the fresh rows, 4 lanes per row (reference order)
     fdis = 0.f;
     if (g.d <= 128)
-        fdis = ref_rows64_4lane_pb<true, 16, 1>(qs, qs, g.storage, g.ld, g.d,
+        fdis = ref_rows64_4lane_pb<!IP, 16, 1>(qs, qs, g.storage, g.ld, g.d,
                                                 lane < nf ? (uint32_t)fv : 0u, nf, lane);
     else if (lane < nf)
-        fdis = l2_row(qs, g.storage + (int64_t)fv * g.ld, g.d);
+        fdis = hnsw_row<IP>(qs, g.storage + (int64_t)fv * g.ld, g.d);
+    if (IP && g.d <= 128) fdis = neg_ip(fdis);  // (the lanes >= nf hold no distance)
     return nf;
 }
 }  // namespace
@@ -563,7 +591,7 @@ __device__ __forceinline__ int seq_fresh_rows(const HNSWDevice& g, const float* 
 // selector, which gates res.add_result alone (:629, :677), so it is read for
 // the seed and for arrivals under the result threshold only.  The arrival log
 // takes members only, since its results are selected from the log.
-template <bool LDS_VISITED, bool GH, bool EXT = false>
+template <bool LDS_VISITED, bool GH, bool EXT = false, bool IP = false>
 __device__ __forceinline__ void hnsw_exact_query(
         HNSWDevice g, const float* __restrict__ x, int ldx, int k, int efSearch, int ef,
         float* __restrict__ D, int64_t* __restrict__ I, int32_t* __restrict__ I32,
@@ -579,7 +607,7 @@ __device__ __forceinline__ void hnsw_exact_query(
     uint32_t* vis = LDS_VISITED ? (uint32_t*)(fi + 64) : vis_global + blk * vwords;
     const int lane = threadIdx.x;
     for (int j = lane; j < qpad; j += 64) qs[j] = j < g.d ? x[q * ldx + j] : 0.f;
-    const uint64_t rinit = sx_key(FLT_MAX, -1);  // heap_heapify<CMax> (Heap.h:316-339)
+    const uint64_t rinit = sx_key<IP>(FLT_MAX, -1);  // heap_heapify<CMax> (Heap.h:316-339)
     for (int j = lane; j < k; j += 64) rb[1 + j] = rinit;
     for (int64_t w = lane; w < vwords; w += 64) vis[w] = 0u;
     // without the result heap (ArrivalLog): the query's arrivals logged in
@@ -599,26 +627,26 @@ __device__ __forceinline__ void hnsw_exact_query(
         // ---- greedy descent (HNSW.cpp:852-924), as in k_hnsw_search
         int nearest = g.entry_point;
         float d_nearest = 0.f;
-        seq_greedy(g, qs, lane, nearest, d_nearest, st_ndis, st_nhops);
+        seq_greedy<IP>(g, qs, lane, nearest, d_nearest, st_ndis, st_nhops);
         // ---- level 0: MinimaxHeap candidates(ef) seeded with the entry;
         // search_from_candidates (:624-637): the seed enters the results
         int hk = 1, nvalid = 1;
         if (lane == 0) {
-            cb[1] = sx_key(d_nearest, nearest);
+            cb[1] = sx_key<IP>(d_nearest, nearest);
             vis[nearest >> 5] |= 1u << (nearest & 31);
         }
         __syncthreads();
-        float rthr = sx_dis(rb[1]);
+        float rthr = sx_dis<IP>(rb[1]);
         const bool seed_in = !EXT || !mask || mask[nearest] != 0;
         int l0steps = 0;  // nstep of search_from_candidates (st_nhops has the greedy hops too)
         if (lg) {
             if (seed_in) {
-                if (lane == 0) lg[0] = sx_key(d_nearest, nearest);
+                if (lane == 0) lg[0] = sx_key<IP>(d_nearest, nearest);
                 lpos = 1;
             }
         } else if (seed_in && d_nearest < rthr) {
-            sx_sift(rb, k, sx_key(d_nearest, nearest), lane);
-            rthr = sx_dis(rb[1]);
+            sx_sift(rb, k, sx_key<IP>(d_nearest, nearest), lane);
+            rthr = sx_dis<IP>(rb[1]);
         }
         const int cnt = g.cum_nb[1] - g.cum_nb[0];
         for (;;) {
@@ -642,7 +670,7 @@ __device__ __forceinline__ void hnsw_exact_query(
                     dc[u] = FLT_MAX;
                     if (i <= hk) {
                         const uint64_t kv = cb[i];
-                        const float dv = sx_dis(kv);
+                        const float dv = sx_dis<IP>(kv);
                         dc[u] = dv;
                         if (sx_id(kv) != -1 && (bp < 0 || dv < bd || (dv == bd && i > bp))) {
                             bd = dv;
@@ -653,7 +681,7 @@ __device__ __forceinline__ void hnsw_exact_query(
             } else {
                 for (int i = 1 + lane; i <= hk; i += 64) {
                     const uint64_t kv = cb[i];
-                    const float dv = sx_dis(kv);
+                    const float dv = sx_dis<IP>(kv);
                     if (sx_id(kv) != -1 && (bp < 0 || dv < bd || (dv == bd && i > bp))) {
                         bd = dv;
                         bp = i;
@@ -677,7 +705,7 @@ __device__ __forceinline__ void hnsw_exact_query(
 #pragma unroll
                 for (int u = 0; u < SX_CACHE; u++) nb += dc[u] < d0;  // (padding: FLT_MAX)
             } else {
-                for (int i = 1 + lane; i <= hk; i += 64) nb += sx_dis(cb[i]) < d0;
+                for (int i = 1 + lane; i <= hk; i += 64) nb += sx_dis<IP>(cb[i]) < d0;
             }
 #pragma unroll
             for (int m = 32; m > 0; m >>= 1) nb += __shfl_xor(nb, m);
@@ -687,7 +715,7 @@ __device__ __forceinline__ void hnsw_exact_query(
                        st_nhops, bp, v0, d0, nb, hk, nvalid, rthr, (unsigned long long)rb[1],
                        (unsigned long long)cb[1]);
 #endif
-            if (lane == 0) cb[bp] = sx_key(d0, -1);
+            if (lane == 0) cb[bp] = sx_key<IP>(d0, -1);
             nvalid--;
             if ((!EXT || check_rel) && nb >= efSearch) {
                 st_n2 = nvalid == 0 ? 1u : 0u;
@@ -696,7 +724,7 @@ __device__ __forceinline__ void hnsw_exact_query(
             // the fresh neighbours of v0 in arrival order and their distances
             int32_t fv;
             float fdis;
-            const int nf = seq_fresh_rows(g, qs, vis, v0, cnt, lane, fv, fdis);
+            const int nf = seq_fresh_rows<IP>(g, qs, vis, v0, cnt, lane, fv, fdis);
             st_ndis += (uint32_t)nf;
             st_nhops += 1;
             // add_to_heap (:678-689) in arrival order; an arrival that can
@@ -707,16 +735,16 @@ __device__ __forceinline__ void hnsw_exact_query(
                 if (EXT && mask) {
                     const bool in = lane < nf && mask[fv] != 0;
                     const unsigned long long im = __ballot(in);
-                    if (in) lg[lpos + __popcll(im & ((1ull << lane) - 1ull))] = sx_key(fdis, fv);
+                    if (in) lg[lpos + __popcll(im & ((1ull << lane) - 1ull))] = sx_key<IP>(fdis, fv);
                     lpos += __popcll(im);
                 } else {
-                    if (lane < nf) lg[lpos + lane] = sx_key(fdis, fv);
+                    if (lane < nf) lg[lpos + lane] = sx_key<IP>(fdis, fv);
                     lpos += nf;
                 }
             }
             for (int t = 0; t < nf; t++) {
                 const float dis = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fdis), t));
-                const bool cin = hk < ef || dis < sx_dis(top);
+                const bool cin = hk < ef || dis < sx_dis<IP>(top);
                 bool rin = !lg && dis < rthr;
                 if (!rin && !cin) continue;
                 const int32_t id = __builtin_amdgcn_readlane(fv, t);
@@ -724,10 +752,10 @@ __device__ __forceinline__ void hnsw_exact_query(
                     rin = false;
                     if (!cin) continue;
                 }
-                const uint64_t key = sx_key(dis, id);
+                const uint64_t key = sx_key<IP>(dis, id);
                 if (rin) {
                     sx_sift(rb, k, key, lane);  // res.add_result: heap_replace_top
-                    rthr = sx_dis(rb[1]);
+                    rthr = sx_dis<IP>(rb[1]);
                 }
                 // MinimaxHeap::push (:1096-1107)
                 if (!cin) continue;
@@ -821,6 +849,21 @@ __device__ __forceinline__ void hnsw_exact_query(
             replay = nle > k;
             nsel = k;
         }
+        if (IP && !replay) {
+            // res.add_result admits dis < FLT_MAX alone: a NaN arrival (above
+            // FLT_MAX in key order, neg_ip) is no result
+            const uint32_t tmax = (uint32_t)(sx_key<IP>(FLT_MAX, -1) >> 32) - 1u;
+            if (T > tmax) {
+                T = tmax;
+                int64_t nle = 0;
+                for (int64_t i0 = 0; i0 < L; i0 += 64) {
+                    const int64_t i = i0 + lane;
+                    const uint32_t bits = i < L ? (uint32_t)(lg[i] >> 32) : 0xffffffffu;
+                    nle += __popcll(__ballot(i < L && bits <= T));
+                }
+                nsel = (int)min<int64_t>(nle, (int64_t)nsel);
+            }
+        }
         if (replay) {
             // heap_heapify + every arrival through res.add_result, in order
             for (int j = lane; j < k; j += 64) rb[1 + j] = rinit;
@@ -834,9 +877,9 @@ __device__ __forceinline__ void hnsw_exact_query(
                     const uint64_t kt =
                             ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(e >> 32), t) << 32) |
                             (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)e, t);
-                    if (sx_dis(kt) < rt) {
+                    if (sx_dis<IP>(kt) < rt) {
                         sx_sift(rb, k, kt, lane);
-                        rt = sx_dis(rb[1]);
+                        rt = sx_dis<IP>(rb[1]);
                     }
                 }
             }
@@ -875,10 +918,10 @@ __device__ __forceinline__ void hnsw_exact_query(
                 float dv = FLT_MAX;
                 int32_t id = -1;
                 if (j < nsel) {
-                    dv = sx_dis(sb[j]);
+                    dv = sx_dis<IP>(sb[j]);
                     id = sx_id(sb[j]);
                 }
-                if (D) D[qo * k + j] = dv;
+                if (D) D[qo * k + j] = IP ? -dv : dv;
                 if (I) I[qo * k + j] = id;
                 if (I32) I32[qo * k + j] = id;
             }
@@ -900,16 +943,16 @@ __device__ __forceinline__ void hnsw_exact_query(
         int32_t id = -1;
         if (j < ii) {
             const uint64_t kv = rb[1 + k - ii + j];
-            dv = sx_dis(kv);
+            dv = sx_dis<IP>(kv);
             id = sx_id(kv);
         }
-        if (D) D[qo * k + j] = dv;
+        if (D) D[qo * k + j] = IP ? -dv : dv;
         if (I) I[qo * k + j] = id;
         if (I32) I32[qo * k + j] = id;
     }
 }
 
-template <bool LDS_VISITED, bool GH = false, bool EXT = false>
+template <bool LDS_VISITED, bool GH = false, bool EXT = false, bool IP = false>
 __global__ __launch_bounds__(64) void k_hnsw_exact(HNSWDevice g, const float* __restrict__ x,
                                                    int ldx, int64_t n, int k, int efSearch,
                                                    int ef, float* __restrict__ D,
@@ -928,7 +971,7 @@ __global__ __launch_bounds__(64) void k_hnsw_exact(HNSWDevice g, const float* __
     const int64_t qo = blockIdx.x;
     if (only && only[q] == 0u) return;
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    hnsw_exact_query<LDS_VISITED, GH, EXT>(g, x, ldx, k, efSearch, ef, D, I, I32, vis_global,
+    hnsw_exact_query<LDS_VISITED, GH, EXT, IP>(g, x, ldx, k, efSearch, ef, D, I, I32, vis_global,
                                            vwords, stats, gheap, alog, q, qo,
                                            (int64_t)blockIdx.x, sm, check_rel, mask);
 }
@@ -999,7 +1042,7 @@ __device__ __forceinline__ void ub_push(const UbHeap& h, int n, uint64_t val, in
 }
 }  // namespace
 
-template <bool LDS_VISITED>
+template <bool LDS_VISITED, bool IP = false>
 __global__ __launch_bounds__(64) void k_hnsw_unbounded(
         HNSWDevice g, const float* __restrict__ x, int ldx, int64_t n, int k, int ef,
         float* __restrict__ D, int64_t* __restrict__ I, int32_t* __restrict__ I32,
@@ -1027,11 +1070,11 @@ __global__ __launch_bounds__(64) void k_hnsw_unbounded(
     if (g.entry_point >= 0) {
         int nearest = g.entry_point;
         float d_nearest = 0.f;
-        seq_greedy(g, qs, lane, nearest, d_nearest, st_ndis, st_nhops);
+        seq_greedy<IP>(g, qs, lane, nearest, d_nearest, st_ndis, st_nhops);
         // the seed enters both queues (:755-758)
         if (lane == 0) {
-            T.lds[1] = sx_key(d_nearest, nearest);
-            C.lds[1] = ~sx_key(d_nearest, nearest);
+            T.lds[1] = sx_key<IP>(d_nearest, nearest);
+            C.lds[1] = ~sx_key<IP>(d_nearest, nearest);
             vis[nearest >> 5] |= 1u << (nearest & 31);
         }
         ts = cs = 1;
@@ -1040,19 +1083,19 @@ __global__ __launch_bounds__(64) void k_hnsw_unbounded(
         uint64_t ttop = T.lds[1];
         while (cs > 0) {
             const uint64_t ck = ~C.lds[1];
-            if (sx_dis(ck) > sx_dis(ttop)) break;  // distance only (:765)
+            if (sx_dis<IP>(ck) > sx_dis<IP>(ttop)) break;  // distance only (:765)
             ub_sift(C, cs, *C.at(cs), lane);  // candidates.pop()
             cs--;
             int32_t fv;
             float fdis;
-            const int nf = seq_fresh_rows(g, qs, vis, sx_id(ck), cnt, lane, fv, fdis);
+            const int nf = seq_fresh_rows<IP>(g, qs, vis, sx_id(ck), cnt, lane, fv, fdis);
             st_ndis += (uint32_t)nf;
             st_nhops += 1;
             // add_to_heap (:789-799) in arrival order
             for (int t = 0; t < nf; t++) {
                 const float dis = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fdis), t));
-                if (!(sx_dis(ttop) > dis || ts < ef)) continue;
-                const uint64_t key = sx_key(dis, __builtin_amdgcn_readlane(fv, t));
+                if (!(sx_dis<IP>(ttop) > dis || ts < ef)) continue;
+                const uint64_t key = sx_key<IP>(dis, __builtin_amdgcn_readlane(fv, t));
                 ub_push(C, ++cs, ~key, lane);
                 // push, then pop while over ef: at ef entries the key replaces
                 // the maximum, which it precedes (dis < the maximum's)
@@ -1080,7 +1123,7 @@ __global__ __launch_bounds__(64) void k_hnsw_unbounded(
         ts--;
     }
     for (int j = ts + lane; j < k; j += 64) {
-        if (D) D[qo * k + j] = FLT_MAX;
+        if (D) D[qo * k + j] = IP ? -FLT_MAX : FLT_MAX;
         if (I) I[qo * k + j] = -1;
         if (I32) I32[qo * k + j] = -1;
     }
@@ -1089,7 +1132,7 @@ __global__ __launch_bounds__(64) void k_hnsw_unbounded(
         ub_sift(T, ts, *T.at(ts), lane);
         ts--;
         if (lane == 0) {
-            if (D) D[qo * k + ts] = sx_dis(top);
+            if (D) D[qo * k + ts] = IP ? -sx_dis<IP>(top) : sx_dis<IP>(top);
             if (I) I[qo * k + ts] = sx_id(top);
             if (I32) I32[qo * k + ts] = sx_id(top);
         }
@@ -1108,10 +1151,24 @@ __global__ __launch_bounds__(64) void k_hnsw_unbounded(
 // exact outcome (tests/test_hnsw_wave_heap.py restates them lane by lane
 // against the serial loops, dead MinimaxHeap slots and ties included).
 namespace {
-__device__ __forceinline__ uint64_t hkey(float d, int32_t id) {
-    return ((uint64_t)(uint32_t)__float_as_int(d) << 32) | (uint32_t)(id ^ 0x80000000);
+// IP: the distance -<q, y> is signed, so its bits go through the usual
+// order-preserving map (negative: all bits flipped, else the sign bit set)
+// and a key's high word orders as unsigned for both metrics
+template <bool IP>
+__device__ __forceinline__ uint32_t hbits(float d) {
+    const uint32_t b = (uint32_t)__float_as_int(d);
+    return IP ? b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u) : b;
 }
-__device__ __forceinline__ float hkey_dis(uint64_t k) { return __int_as_float((int)(k >> 32)); }
+template <bool IP>
+__device__ __forceinline__ float hbits_dis(uint32_t b) {
+    return __int_as_float((int)(IP ? b ^ ((uint32_t)((int32_t)~b >> 31) | 0x80000000u) : b));
+}
+template <bool IP = false>
+__device__ __forceinline__ uint64_t hkey(float d, int32_t id) {
+    return ((uint64_t)hbits<IP>(d) << 32) | (uint32_t)(id ^ 0x80000000);
+}
+template <bool IP = false>
+__device__ __forceinline__ float hkey_dis(uint64_t k) { return hbits_dis<IP>((uint32_t)(k >> 32)); }
 __device__ __forceinline__ int32_t hkey_id(uint64_t k) { return (int32_t)((uint32_t)k ^ 0x80000000u); }
 constexpr uint32_t HKEY_DEAD_LO = 0x7fffffffu;  // id -1
 __device__ __forceinline__ uint64_t rotr1(uint64_t m) { return (m >> 1) | (m << 63); }
@@ -1219,16 +1276,18 @@ struct SortedQ {
 //    distance is shared (which of them is the top).  CandSet reports either
 //    case (returns false) and the query is searched again with CandLayout;
 //    otherwise it evolves exactly as the heap's set does.
-struct CandLayout {
+template <bool IP>
+struct CandLayoutT {
+    static constexpr bool kIP = IP;
     static constexpr bool kMerge = false;
     KHeap h;
     int hk;
     __device__ __forceinline__ void init(int) {
-        h.key = hkey(FLT_MAX, -1);
+        h.key = hkey<IP>(FLT_MAX, -1);
         hk = 0;
     }
     __device__ __forceinline__ void seed(uint64_t nk, int lane) { h.push(++hk, nk, lane); }
-    __device__ __forceinline__ float top_dis() const { return hkey_dis(h.at(1)); }
+    __device__ __forceinline__ float top_dis() const { return hkey_dis<IP>(h.at(1)); }
     // pop_min + count_below(d0) (:1299-1342): the smallest alive distance,
     // the highest position among equal ones (distances >= 0: their bits
     // order as unsigned)
@@ -1259,7 +1318,7 @@ struct CandLayout {
     __device__ __forceinline__ bool push(int ef, uint64_t nk, float dis, int& nvalid, int lane) {
         if (hk == ef) {
             const uint64_t top = h.at(1);
-            if (dis >= hkey_dis(top)) return true;
+            if (dis >= hkey_dis<IP>(top)) return true;
             if ((uint32_t)top != HKEY_DEAD_LO) --nvalid;
             h.pop(hk--, lane);
         }
@@ -1268,14 +1327,17 @@ struct CandLayout {
         return true;
     }
 };
-struct CandSet {
+using CandLayout = CandLayoutT<false>;
+template <bool IP>
+struct CandSetT {
+    static constexpr bool kIP = IP;
     static constexpr bool kMerge = true;
     uint64_t key;    // lane j < hk: the j-th entry by (distance, id)
     uint64_t amask;  // the alive entries (popped ones stay, as in the heap)
     int hk;
     int kres;        // k of the results: they are derived from this set (below)
     __device__ __forceinline__ void init(int k) {
-        key = hkey(FLT_MAX, -1);
+        key = hkey<IP>(FLT_MAX, -1);
         amask = 0ull;
         hk = 0;
         kres = k;
@@ -1293,7 +1355,7 @@ struct CandSet {
         amask = open_bit(amask, pos);
     }
     __device__ __forceinline__ void seed(uint64_t nk, int lane) { insert(hk++, nk, lane); }
-    __device__ __forceinline__ float top_dis() const { return hkey_dis(rdlane64(key, hk - 1)); }
+    __device__ __forceinline__ float top_dis() const { return hkey_dis<IP>(rdlane64(key, hk - 1)); }
     __device__ __forceinline__ uint64_t peek_min(int lane) const {
         return amask ? rdlane64(key, __builtin_ctzll(amask)) : ~0ull;
     }
@@ -1310,13 +1372,13 @@ struct CandSet {
     __device__ __forceinline__ bool push(int ef, uint64_t nk, float dis, int& nvalid, int lane) {
         if (hk == ef) {
             const uint64_t top = rdlane64(key, hk - 1);
-            if (dis >= hkey_dis(top)) return true;
+            if (dis >= hkey_dis<IP>(top)) return true;
         }
         // results smaller than the set (k < ef) keep, among equal distances,
         // the earliest arrivals, not the smallest ids: an arrival equal to a
         // kept entry ends this form
         if (kres < ef &&
-            __ballot(lane < hk && (uint32_t)(key >> 32) == (uint32_t)__float_as_int(dis)))
+            __ballot(lane < hk && (uint32_t)(key >> 32) == hbits<IP>(dis)))
             return false;
         if (hk == ef) {
             // the heap's top among several entries of the largest distance
@@ -1337,10 +1399,11 @@ struct CandSet {
     // admission): every entry of this set below FLT_MAX that ranks < k — the
     // set holds the ef >= k smallest arrivals, the results the k smallest
     __device__ __forceinline__ void results(SortedQ& R, int k, int lane) const {
-        const bool v = lane < hk && lane < k && (uint32_t)(key >> 32) < 0x7f7fffffu;
-        R.key = v ? key : hkey(FLT_MAX, -1);
+        const bool v = lane < hk && lane < k && (uint32_t)(key >> 32) < hbits<IP>(FLT_MAX);
+        R.key = v ? key : hkey<IP>(FLT_MAX, -1);
     }
 };
+using CandSet = CandSetT<false>;
 // One hop's add_to_heap calls for the arrivals `todo` (lanes, arrival order)
 // as one merge into CandSet: when no two of the distances involved are equal
 // (the arrivals' among themselves and with the kept entries), the sequential
@@ -1351,10 +1414,11 @@ struct CandSet {
 // places in order.  False (nothing changed) on any equality, or on a tie
 // inside the set when the merge evicts: then the hop runs the sequential
 // pushes.
-__device__ __forceinline__ bool hop_merge(CandSet& C, int ef, unsigned long long todo, float fdis,
+template <bool IP>
+__device__ __forceinline__ bool hop_merge(CandSetT<IP>& C, int ef, unsigned long long todo, float fdis,
                                           int32_t fv, int lane, int& nvalid) {
     const uint32_t cd = (uint32_t)(C.key >> 32);
-    const uint32_t fd = (uint32_t)__float_as_int(fdis);
+    const uint32_t fd = hbits<IP>(fdis);
     const int hk = C.hk, m = __popcll(todo);
     const uint64_t cm = hk >= 64 ? ~0ull : ((1ull << hk) - 1ull);
     if (hk + m > ef) {
@@ -1378,7 +1442,7 @@ __device__ __forceinline__ bool hop_merge(CandSet& C, int ef, unsigned long long
     const int na = __popcll(da & lt);
     const bool isa = (da >> lane) & 1ull;
     const int al = __builtin_amdgcn_ds_bpermute(na << 2, arr);
-    const uint64_t fa = bperm64(hkey(fdis, fv), al);
+    const uint64_t fa = bperm64(hkey<IP>(fdis, fv), al);
     const int src = (lane - na) & 63;
     const uint64_t fc = bperm64(C.key, src);
     C.key = isa ? fa : fc;
@@ -1587,10 +1651,10 @@ template <class CQ>
 __device__ __forceinline__ void level0_seed(CQ& C, SortedQ& R, L0Run& S, uint32_t* vis, int k,
                                             int lane, int nearest, float d_nearest) {
     C.init(k);
-    C.seed(hkey(d_nearest, nearest), lane);
-    if (d_nearest < FLT_MAX) R.insert(k, hkey(d_nearest, nearest), lane);
+    C.seed(hkey<CQ::kIP>(d_nearest, nearest), lane);
+    if (d_nearest < FLT_MAX) R.insert(k, hkey<CQ::kIP>(d_nearest, nearest), lane);
     S.nvalid = 1;
-    S.rmax = hkey_dis(rdlane64(R.key, k - 1));
+    S.rmax = hkey_dis<CQ::kIP>(rdlane64(R.key, k - 1));
     S.todo = 0ull;
     S.logpos = 0;
     if (lane == 0) vis[nearest >> 5] |= 1u << (nearest & 31);
@@ -1621,11 +1685,11 @@ __device__ __forceinline__ bool hnsw_level0(const HNSWDevice& g, const float* qs
             const int t = __builtin_ctzll(todo);
             const int32_t vt = __builtin_amdgcn_readlane(fv, t);
             const float dis = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fdis), t));
-            const uint64_t nk = hkey(dis, vt);
+            const uint64_t nk = hkey<CQ::kIP>(dis, vt);
             if (!C.push(ef, nk, dis, nvalid, lane)) {
                 if constexpr (CQ::kMerge) {
                     C.results(R, k, lane);
-                    rmax = hkey_dis(rdlane64(R.key, k - 1));
+                    rmax = hkey_dis<CQ::kIP>(rdlane64(R.key, k - 1));
                 }
                 S.nvalid = nvalid;
                 S.rmax = rmax;
@@ -1639,7 +1703,7 @@ __device__ __forceinline__ bool hnsw_level0(const HNSWDevice& g, const float* qs
             if constexpr (!CQ::kMerge) {  // (CandSet: the results are derived from it)
                 if (dis < rmax) {
                     R.insert(k, nk, lane);
-                    rmax = hkey_dis(rdlane64(R.key, k - 1));
+                    rmax = hkey_dis<CQ::kIP>(rdlane64(R.key, k - 1));
                 }
             }
         }
@@ -1663,7 +1727,7 @@ __device__ __forceinline__ bool hnsw_level0(const HNSWDevice& g, const float* qs
             if (!C.pop_min(lane, v0, nb)) {
                 if constexpr (CQ::kMerge) {
                     C.results(R, k, lane);
-                    rmax = hkey_dis(rdlane64(R.key, k - 1));
+                    rmax = hkey_dis<CQ::kIP>(rdlane64(R.key, k - 1));
                 }
                 S.nvalid = nvalid;
                 S.rmax = rmax;
@@ -1712,7 +1776,7 @@ __device__ __forceinline__ bool hnsw_level0(const HNSWDevice& g, const float* qs
             // fall during the hop)
             const bool full0 = C.hk == ef;
             const float ctop0 = full0 ? C.top_dis() : FLT_MAX;
-            if (NB0 && g.q8 && full0 && nf > 0) {
+            if (!CQ::kIP && NB0 && g.q8 && full0 && nf > 0) {
                 // int8 lower bounds first: only the rows that may enter a
                 // heap have their fp32 row read (c4: ~5 of ~42 per hop)
                 int32_t sv;
@@ -1729,14 +1793,15 @@ __device__ __forceinline__ bool hnsw_level0(const HNSWDevice& g, const float* qs
             float fdis = 0.f;
             if (g.d <= 128)
 #if HNSW_FP32_8LANE
-                fdis = ref_rows64_8lane<true, 16>(qs, qs, g.storage, g.ld, g.d,
+                fdis = ref_rows64_8lane<!CQ::kIP, 16>(qs, qs, g.storage, g.ld, g.d,
                                                   lane < nf ? (uint32_t)fv : 0u, nf, lane);
 #else
-                fdis = ref_rows64_4lane_pb<true, 16, HNSW_PB>(qs, qs, g.storage, g.ld, g.d,
+                fdis = ref_rows64_4lane_pb<!CQ::kIP, 16, HNSW_PB>(qs, qs, g.storage, g.ld, g.d,
                                                         lane < nf ? (uint32_t)fv : 0u, nf, lane);
 #endif
             else if (lane < nf)
-                fdis = l2_row(qs, g.storage + (int64_t)fv * g.ld, g.d);
+                fdis = hnsw_row<CQ::kIP>(qs, g.storage + (int64_t)fv * g.ld, g.d);
+            if (CQ::kIP && g.d <= 128) fdis = neg_ip(fdis);  // (the lanes >= nf hold no distance)
             st_nhops += 1;
             if (TRACE) {
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -1752,11 +1817,11 @@ __device__ __forceinline__ bool hnsw_level0(const HNSWDevice& g, const float* qs
             if (NB0) {
                 // next pop: the closest arrival if it enters and beats the
                 // closest alive candidate, else that candidate
-                const uint32_t fb = lane < nf ? (uint32_t)__float_as_int(fdis) : 0xffffffffu;
+                const uint32_t fb = lane < nf ? hbits<CQ::kIP>(fdis) : 0xffffffffu;
                 const uint32_t amin = wave_min_u32(fb);
                 const uint64_t cmin = C.peek_min(lane);
                 int32_t pred = cmin != ~0ull ? hkey_id(cmin) : -1;
-                if (nf > 0 && (!full0 || __int_as_float((int)amin) < ctop0) &&
+                if (nf > 0 && (!full0 || hbits_dis<CQ::kIP>(amin) < ctop0) &&
                     amin < (uint32_t)(cmin >> 32))
                     pred = __builtin_amdgcn_readlane(
                             fv, __builtin_ctzll(__ballot(lane < nf && fb == amin)));
@@ -1782,13 +1847,13 @@ __device__ __forceinline__ bool hnsw_level0(const HNSWDevice& g, const float* qs
                         // after a tie (~1.5 % of c4's queries)
                         if (lane == 0) __builtin_nontemporal_store(RLOG_POP, rlog + hp);
                         if ((todo >> lane) & 1ull)
-                            __builtin_nontemporal_store(hkey(fdis, fv),
+                            __builtin_nontemporal_store(hkey<CQ::kIP>(fdis, fv),
                                                         rlog + hp + 1 + __popcll(todo & lt));
                     }
                     S.logpos = hp + 1 + m;
                 }
                 if (TRACE) tr.tick(14);
-                if (todo && hop_merge(C, ef, todo, fdis, fv, lane, nvalid)) todo = 0ull;
+                if (todo && hop_merge<CQ::kIP>(C, ef, todo, fdis, fv, lane, nvalid)) todo = 0ull;
             }
             if (todo && !apply(todo, hop_todo, fdis, fv, hp)) return false;
         }
@@ -1807,11 +1872,12 @@ __device__ __forceinline__ bool hnsw_level0(const HNSWDevice& g, const float* qs
 // means the log is corrupt: the replay stops there and returns the number of
 // such entries read (the caller then searches level 0 again and counts it in
 // the `replay_bad` statistic, which the tests assert to be 0).
-__device__ __forceinline__ int level0_replay(CandLayout& C, const uint64_t* __restrict__ rlog,
+template <class CL>
+__device__ __forceinline__ int level0_replay(CL& C, const uint64_t* __restrict__ rlog,
                                              int stop, int ef, int ntotal, int lane,
                                              int nearest, float d_nearest) {
     C.init(0);
-    C.seed(hkey(d_nearest, nearest), lane);
+    C.seed(hkey<CL::kIP>(d_nearest, nearest), lane);
     int dummy = 0;
     for (int base = 0; base < stop; base += 64) {
         const uint64_t e = base + lane < stop ? rlog[base + lane] : RLOG_POP;
@@ -1828,7 +1894,7 @@ __device__ __forceinline__ int level0_replay(CandLayout& C, const uint64_t* __re
                 int nb;
                 C.pop_min(lane, v0, nb);
             } else {
-                C.push(ef, v, hkey_dis(v), dummy, lane);
+                C.push(ef, v, hkey_dis<CL::kIP>(v), dummy, lane);
             }
         }
     }
@@ -1842,7 +1908,7 @@ __device__ __forceinline__ int level0_replay(CandLayout& C, const uint64_t* __re
 // (rlog, or the LDS when LOGLDS), or searches level 0 again when the log
 // overflowed (layout = 1: every query with CandLayout — tests).  Results are
 // the reference's, bit for bit, either way.
-template <bool LDS_VISITED, bool TRACE, bool NB0, bool LOGLDS>
+template <bool LDS_VISITED, bool TRACE, bool NB0, bool LOGLDS, bool IP = false>
 __global__ __launch_bounds__(64, HNSW_WPE) void k_hnsw_exact_reg(HNSWDevice g, const float* __restrict__ x,
                                                        int ldx, int64_t n, int k, int efSearch,
                                                        int ef, float* __restrict__ D,
@@ -1880,9 +1946,9 @@ __global__ __launch_bounds__(64, HNSW_WPE) void k_hnsw_exact_reg(HNSWDevice g, c
     for (int j = lane; j < qpad; j += 64) qs[j] = j < g.d ? x[q * ldx + j] : 0.f;
     for (int64_t w = lane; w < vwords; w += 64) vis[w] = 0u;
     SortedQ R;  // results: heap_heapify<CMax> (Heap.h:316-339) = k x (FLT_MAX, -1)
-    R.key = hkey(FLT_MAX, -1);
+    R.key = hkey<IP>(FLT_MAX, -1);
     __syncthreads();
-    if (NB0 && g.q8) {
+    if (!IP && NB0 && g.q8) {
         q8_query_prep(qs, g.d, q8x, q8d, lane);
         __syncthreads();
     }
@@ -1891,7 +1957,7 @@ __global__ __launch_bounds__(64, HNSW_WPE) void k_hnsw_exact_reg(HNSWDevice g, c
     if (g.entry_point >= 0) {
         // ---- greedy descent (HNSW.cpp:852-924), as in k_hnsw_search
         int nearest = g.entry_point;
-        float d_nearest = l2_row(qs, g.storage + (int64_t)nearest * g.ld, g.d);
+        float d_nearest = hnsw_row<IP>(qs, g.storage + (int64_t)nearest * g.ld, g.d);
         for (int level = g.max_level; level >= 1; level--) {
             for (;;) {
                 const uint64_t o = g.offsets[nearest];
@@ -1902,7 +1968,7 @@ __global__ __launch_bounds__(64, HNSW_WPE) void k_hnsw_exact_reg(HNSWDevice g, c
                         __ballot(lane < cnt && v < 0) | (cnt < 64 ? (~0ull << cnt) : 0ull);
                 const int first_neg = neg ? __ffsll((long long)neg) - 1 : 64;
                 float dis = WS_INF;
-                if (lane < first_neg) dis = l2_row(qs, g.storage + (int64_t)v * g.ld, g.d);
+                if (lane < first_neg) dis = hnsw_row<IP>(qs, g.storage + (int64_t)v * g.ld, g.d);
                 st_ndis += (uint32_t)min(first_neg, 64);
                 st_nhops += 1;
                 float md = dis;
@@ -1935,14 +2001,14 @@ __global__ __launch_bounds__(64, HNSW_WPE) void k_hnsw_exact_reg(HNSWDevice g, c
         L0Run S;
         bool done = false;
         if (!layout) {
-            CandSet C;
+            CandSetT<IP> C;
             level0_seed(C, R, S, vis, k, lane, nearest, d_nearest);
-            done = hnsw_level0<CandSet, TRACE, NB0>(g, qs, vis, k, efSearch, ef, lane, C, S, R, st_n2,
+            done = hnsw_level0<CandSetT<IP>, TRACE, NB0>(g, qs, vis, k, efSearch, ef, lane, C, S, R, st_n2,
                                                st_ndis, st_nhops, tr, qlog, q8x, q8d, st_q8,
                                                st_x32, logcap);
         }
         if (!done) {
-            CandLayout C;
+            CandLayoutT<IP> C;
             if (TRACE) tr.t[8] = 1;
             int how = 1;  // 0: replayed, 1: log overflowed or absent, 2: log corrupt
             if (!layout && qlog && S.logpos <= logcap) {
@@ -1958,7 +2024,7 @@ __global__ __launch_bounds__(64, HNSW_WPE) void k_hnsw_exact_reg(HNSWDevice g, c
                 // again from the start: fresh visited table, results, counters
                 __syncthreads();
                 for (int64_t w = lane; w < vwords; w += 64) vis[w] = 0u;
-                R.key = hkey(FLT_MAX, -1);
+                R.key = hkey<IP>(FLT_MAX, -1);
                 st_n2 = 0;
                 st_ndis = up_ndis;
                 st_nhops = up_nhops;
@@ -1966,7 +2032,7 @@ __global__ __launch_bounds__(64, HNSW_WPE) void k_hnsw_exact_reg(HNSWDevice g, c
                 __syncthreads();
                 level0_seed(C, R, S, vis, k, lane, nearest, d_nearest);
             }
-            hnsw_level0<CandLayout, TRACE, NB0>(g, qs, vis, k, efSearch, ef, lane, C, S, R, st_n2,
+            hnsw_level0<CandLayoutT<IP>, TRACE, NB0>(g, qs, vis, k, efSearch, ef, lane, C, S, R, st_n2,
                                                 st_ndis, st_nhops, tr, nullptr, q8x, q8d, st_q8,
                                                 st_x32, 0);
         }
@@ -1987,7 +2053,8 @@ __global__ __launch_bounds__(64, HNSW_WPE) void k_hnsw_exact_reg(HNSWDevice g, c
     // placeholders (id -1) after them as (FLT_MAX, -1)
     if (lane < k) {
         const int32_t id = hkey_id(R.key);
-        const float dv = id != -1 ? hkey_dis(R.key) : FLT_MAX;
+        float dv = id != -1 ? hkey_dis<IP>(R.key) : FLT_MAX;
+        if (IP) dv = -dv;  // the inner products, (-FLT_MAX, -1) padding
         if (D) D[qo * k + lane] = dv;
         if (I) I[qo * k + lane] = id;
         if (I32) I32[qo * k + lane] = id;
@@ -2499,14 +2566,16 @@ static ArrivalLog make_arrival_log(const HNSWDevice& g, int k, int ef, void* alo
     return al;
 }
 // the sequential kernel over n queries (qidx: the listed ones, compact
-// outputs), register heaps for ef, k <= 64
-static void hnsw_exact_launch(const HNSWDevice& g, const float* x, int ldx, int64_t n, int k,
+// outputs), register heaps for ef, k <= 64; IP: the inner-product
+// instantiations (mode.inner_product), the same choice of form
+template <bool IP>
+static void hnsw_exact_launch_t(const HNSWDevice& g, const float* x, int ldx, int64_t n, int k,
                               int efSearch, float* D, int64_t* I, int32_t* I32,
                               uint32_t* visited_scratch, int64_t vwords,
                               unsigned long long* stats, const uint32_t* only,
-                              const uint32_t* qidx, hipStream_t s, float* gheap = nullptr,
-                              uint64_t* rlog = nullptr, int rcap = 0, void* alog = nullptr,
-                              size_t alog_bytes = 0, const HNSWMode& mode = HNSWMode{}) {
+                              const uint32_t* qidx, hipStream_t s, float* gheap,
+                              uint64_t* rlog, int rcap, void* alog, size_t alog_bytes,
+                              const HNSWMode& mode) {
     const int ef = efSearch > k ? efSearch : k;
     if (!mode.bounded_queue) {
         // search_from_candidate_unbounded: its own kernel, both queues' tails
@@ -2514,10 +2583,10 @@ static void hnsw_exact_launch(const HNSWDevice& g, const float* x, int ldx, int6
         FAISS_THROW_IF_NOT(gheap != nullptr && only == nullptr);
         const size_t lds_u = ub_lds_bytes(g.ld, ef, g.ntotal);
         if (lds_u + vwords * 4 <= 64 * 1024)
-            k_hnsw_unbounded<true><<<kgrid(n, 64), dim3(64), lds_u + vwords * 4, s>>>(
+            k_hnsw_unbounded<true, IP><<<kgrid(n, 64), dim3(64), lds_u + vwords * 4, s>>>(
                     g, x, ldx, n, k, ef, D, I, I32, nullptr, vwords, stats, qidx, (uint64_t*)gheap);
         else
-            k_hnsw_unbounded<false><<<kgrid(n, 64), dim3(64), lds_u, s>>>(
+            k_hnsw_unbounded<false, IP><<<kgrid(n, 64), dim3(64), lds_u, s>>>(
                     g, x, ldx, n, k, ef, D, I, I32, visited_scratch, vwords, stats, qidx,
                     (uint64_t*)gheap);
         HIP_LAUNCH_CHECK();
@@ -2525,7 +2594,7 @@ static void hnsw_exact_launch(const HNSWDevice& g, const float* x, int ldx, int6
     }
     const size_t lds_x = seq_lds_bytes(g.ld, ef, k);
     const bool x_lds_vis = lds_x + vwords * 4 <= 64 * 1024;
-    if (!mode.is_default()) {
+    if (!mode.default_level0()) {
         // the stop after efSearch hops and / or a selector: the sequential
         // kernel's EXT form at every ef and k (never the register kernel)
         const bool chk = mode.check_relative_distance;
@@ -2533,21 +2602,21 @@ static void hnsw_exact_launch(const HNSWDevice& g, const float* x, int ldx, int6
             FAISS_THROW_IF_NOT(gheap != nullptr);
             const size_t lds_g = seq_lds_bytes_gheap(g.ld);
             if (lds_g + vwords * 4 <= 64 * 1024)
-                k_hnsw_exact<true, true, true><<<kgrid(n, 64), dim3(64), lds_g + vwords * 4, s>>>(
+                k_hnsw_exact<true, true, true, IP><<<kgrid(n, 64), dim3(64), lds_g + vwords * 4, s>>>(
                         g, x, ldx, n, k, efSearch, ef, D, I, I32, nullptr, vwords, stats, only,
                         qidx, gheap, ArrivalLog{}, chk, mode.mask);
             else
-                k_hnsw_exact<false, true, true><<<kgrid(n, 64), dim3(64), lds_g, s>>>(
+                k_hnsw_exact<false, true, true, IP><<<kgrid(n, 64), dim3(64), lds_g, s>>>(
                         g, x, ldx, n, k, efSearch, ef, D, I, I32, visited_scratch, vwords, stats,
                         only, qidx, gheap, ArrivalLog{}, chk, mode.mask);
         } else {
             const ArrivalLog al = make_arrival_log(g, k, ef, alog, alog_bytes, s);
             if (x_lds_vis)
-                k_hnsw_exact<true, false, true><<<kgrid(n, 64), dim3(64), lds_x + vwords * 4, s>>>(
+                k_hnsw_exact<true, false, true, IP><<<kgrid(n, 64), dim3(64), lds_x + vwords * 4, s>>>(
                         g, x, ldx, n, k, efSearch, ef, D, I, I32, nullptr, vwords, stats, only,
                         qidx, nullptr, al, chk, mode.mask);
             else
-                k_hnsw_exact<false, false, true><<<kgrid(n, 64), dim3(64), lds_x, s>>>(
+                k_hnsw_exact<false, false, true, IP><<<kgrid(n, 64), dim3(64), lds_x, s>>>(
                         g, x, ldx, n, k, efSearch, ef, D, I, I32, visited_scratch, vwords, stats,
                         only, qidx, nullptr, al, chk, mode.mask);
         }
@@ -2560,11 +2629,11 @@ static void hnsw_exact_launch(const HNSWDevice& g, const float* x, int ldx, int6
         FAISS_THROW_IF_NOT(gheap != nullptr);
         const size_t lds_g = seq_lds_bytes_gheap(g.ld);
         if (lds_g + vwords * 4 <= 64 * 1024)
-            k_hnsw_exact<true, true><<<kgrid(n, 64), dim3(64), lds_g + vwords * 4, s>>>(
+            k_hnsw_exact<true, true, false, IP><<<kgrid(n, 64), dim3(64), lds_g + vwords * 4, s>>>(
                     g, x, ldx, n, k, efSearch, ef, D, I, I32, nullptr, vwords, stats, only, qidx,
                     gheap);
         else
-            k_hnsw_exact<false, true><<<kgrid(n, 64), dim3(64), lds_g, s>>>(
+            k_hnsw_exact<false, true, false, IP><<<kgrid(n, 64), dim3(64), lds_g, s>>>(
                     g, x, ldx, n, k, efSearch, ef, D, I, I32, visited_scratch, vwords, stats, only,
                     qidx, gheap);
         HIP_LAUNCH_CHECK();
@@ -2587,8 +2656,9 @@ static void hnsw_exact_launch(const HNSWDevice& g, const float* x, int ldx, int6
                              lds_r + (size_t)vwords * 4 + lds_logb <= 8192;
         const size_t lds_logx = lds_log ? lds_logb : 0;
         // FAISS_AMD_HNSW_TRACE=<file>: per-query hop-phase cycles (profiling)
-        const char* tenv = getenv("FAISS_AMD_HNSW_TRACE");
-        if (tenv && rvis) {
+        // (L2 only)
+        const char* tenv = IP ? nullptr : getenv("FAISS_AMD_HNSW_TRACE");
+        if (!IP && tenv && rvis) {
             unsigned long long* tb = nullptr;
             HIP_CHECK(hipMalloc(&tb, 128 * std::max<int64_t>(n, 1)));
             HIP_CHECK(hipMemsetAsync(tb, 0, 128 * std::max<int64_t>(n, 1), s));
@@ -2609,11 +2679,13 @@ static void hnsw_exact_launch(const HNSWDevice& g, const float* x, int ldx, int6
             }
             return;
         }
-        auto kr = lds_log ? k_hnsw_exact_reg<true, false, true, true>
-                  : rvis  ? (g.nb0 ? k_hnsw_exact_reg<true, false, true, false>
-                                   : k_hnsw_exact_reg<true, false, false, false>)
-                          : (g.nb0 ? k_hnsw_exact_reg<false, false, true, false>
-                                   : k_hnsw_exact_reg<false, false, false, false>);
+        auto kr = rvis ? (g.nb0 ? k_hnsw_exact_reg<true, false, true, false, IP>
+                                : k_hnsw_exact_reg<true, false, false, false, IP>)
+                       : (g.nb0 ? k_hnsw_exact_reg<false, false, true, false, IP>
+                                : k_hnsw_exact_reg<false, false, false, false, IP>);
+        // (inner product: no replay log, so none in the LDS either)
+        if constexpr (!IP)
+            if (lds_log) kr = k_hnsw_exact_reg<true, false, true, true>;
         kr<<<kgrid(n, 64), dim3(64), rvis ? lds_r + vwords * 4 + lds_logx : lds_r, s>>>(
                 g, x, ldx, n, k, efSearch, ef, D, I, I32, rvis ? nullptr : visited_scratch, vwords,
                 stats, only, qidx, layout, nullptr, rlog, rcap);
@@ -2628,14 +2700,32 @@ static void hnsw_exact_launch(const HNSWDevice& g, const float* x, int ldx, int6
     // with k while a replace_top near the heap's top stays shallow)
     const ArrivalLog al = make_arrival_log(g, k, ef, alog, alog_bytes, s);
     if (x_lds_vis)
-        k_hnsw_exact<true><<<kgrid(n, 64), dim3(64), lds_x + vwords * 4, s>>>(
+        k_hnsw_exact<true, false, false, IP><<<kgrid(n, 64), dim3(64), lds_x + vwords * 4, s>>>(
                 g, x, ldx, n, k, efSearch, ef, D, I, I32, nullptr, vwords, stats, only, qidx,
                 nullptr, al);
     else
-        k_hnsw_exact<false><<<kgrid(n, 64), dim3(64), lds_x, s>>>(
+        k_hnsw_exact<false, false, false, IP><<<kgrid(n, 64), dim3(64), lds_x, s>>>(
                 g, x, ldx, n, k, efSearch, ef, D, I, I32, visited_scratch, vwords, stats, only,
                 qidx, nullptr, al);
     HIP_LAUNCH_CHECK();
+}
+static void hnsw_exact_launch(const HNSWDevice& g, const float* x, int ldx, int64_t n, int k,
+                              int efSearch, float* D, int64_t* I, int32_t* I32,
+                              uint32_t* visited_scratch, int64_t vwords,
+                              unsigned long long* stats, const uint32_t* only,
+                              const uint32_t* qidx, hipStream_t s, float* gheap = nullptr,
+                              uint64_t* rlog = nullptr, int rcap = 0, void* alog = nullptr,
+                              size_t alog_bytes = 0, const HNSWMode& mode = HNSWMode{}) {
+    if (mode.inner_product) {
+        // (no int8 image: IndexHNSW::sync_device keeps it to L2; no replay log:
+        // hnsw_register_eligible is false)
+        FAISS_THROW_IF_NOT(g.q8 == nullptr && rlog == nullptr);
+        hnsw_exact_launch_t<true>(g, x, ldx, n, k, efSearch, D, I, I32, visited_scratch, vwords,
+                                  stats, only, qidx, s, gheap, nullptr, 0, alog, alog_bytes, mode);
+    } else {
+        hnsw_exact_launch_t<false>(g, x, ldx, n, k, efSearch, D, I, I32, visited_scratch, vwords,
+                                   stats, only, qidx, s, gheap, rlog, rcap, alog, alog_bytes, mode);
+    }
 }
 size_t hnsw_arrival_log_bytes(int64_t n, int64_t ntotal) {
     // (at most 256 MiB; slots past the pool fall back to the result heap)
@@ -2704,12 +2794,13 @@ bool hnsw_visited_scratch_needed(int ld, int k, int efSearch, int64_t vwords,
     const size_t lds_x = seq_lds_bytes(ld, ef, k);
     const size_t lds_xg = lds_x > kL ? seq_lds_bytes_gheap(ld) : lds_x;
     bool need = lds_xg + vb > kL;
-    if (!mode.is_default()) return need;  // the sequential kernel alone
+    if (!mode.default_level0()) return need;  // the sequential kernel alone
     if (ef <= 64 && k <= 64 && lds_x <= kL) {
         HNSWDevice g{};
         g.ld = ld;
         need = need || (size_t)exact_reg_head(g) + vb > kL;
     }
+    if (mode.inner_product) return need;  // the sequential and register kernels alone
     if (hnsw_uses_wide(k, efSearch)) {
         HNSWDevice g{};
         g.ld = ld;

@@ -5,8 +5,14 @@
 // and the objects `make -C oracle/ref full` leaves under oracle/_ref/fobj, into
 // oracle/_ref/ (never committed, never linked into the product).
 //
-//   hnsw_params_driver build <factory> <d> <nb> <xb.f32> <out.faiss>
+//   hnsw_params_driver build <factory> <d> <nb> <xb.f32> <out.faiss> [l2|ip]
 //   hnsw_params_driver run <index.faiss> <d> <nq> <xq.f32> <jobs.txt> <outdir>
+//   hnsw_params_driver coarse <index.faiss> <d> <nq> <xq.f32> <efSearch> <k> <out.bin>
+//
+// build: the metric defaults to l2; an index that needs training (IVF) is
+// trained on xb before the add.  coarse: the IndexIVF's quantizer (an
+// IndexHNSW) searched on its own at efSearch; out.bin as a job's, without
+// the stats.
 //
 // jobs.txt, one case per line:
 //   name k how efSearch check bounded sel nprobe
@@ -77,8 +83,12 @@ Sel parse_sel(const std::string& spec) {
 int build(char** a) {
     const int d = atoi(a[1]);
     const size_t nb = (size_t)atoll(a[2]);
-    std::unique_ptr<faiss::Index> ix(faiss::index_factory(d, a[0]));
+    const std::string metric = a[5] ? a[5] : "l2";
+    if (metric != "l2" && metric != "ip") throw std::runtime_error("bad metric: " + metric);
+    std::unique_ptr<faiss::Index> ix(faiss::index_factory(
+            d, a[0], metric == "ip" ? faiss::METRIC_INNER_PRODUCT : faiss::METRIC_L2));
     const std::vector<float> xb = read_f32(a[3], nb * d);
+    if (!ix->is_trained) ix->train((faiss::idx_t)nb, xb.data());
     ix->add((faiss::idx_t)nb, xb.data());
     faiss::write_index(ix.get(), a[4]);
     return 0;
@@ -147,13 +157,35 @@ int run(char** a) {
     return 0;
 }
 
+int coarse(char** a) {
+    std::unique_ptr<faiss::Index> ix(faiss::read_index(a[0]));
+    const int d = atoi(a[1]);
+    const size_t nq = (size_t)atoll(a[2]);
+    const std::vector<float> xq = read_f32(a[3], nq * d);
+    auto* ivf = dynamic_cast<faiss::IndexIVF*>(ix.get());
+    auto* hx = ivf ? dynamic_cast<faiss::IndexHNSW*>(ivf->quantizer) : nullptr;
+    if (!hx) throw std::runtime_error("no IndexIVF over an IndexHNSW");
+    hx->hnsw.efSearch = atoi(a[4]);
+    const size_t k = (size_t)atoll(a[5]);
+    std::vector<float> D(nq * k);
+    std::vector<faiss::idx_t> I(nq * k);
+    hx->search((faiss::idx_t)nq, xq.data(), (faiss::idx_t)k, D.data(), I.data());
+    std::ofstream o(a[6], std::ios::binary);
+    o.write(reinterpret_cast<const char*>(D.data()), (std::streamsize)(D.size() * sizeof(float)));
+    o.write(reinterpret_cast<const char*>(I.data()),
+            (std::streamsize)(I.size() * sizeof(faiss::idx_t)));
+    if (!o) throw std::runtime_error("write failed");
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     omp_set_num_threads(1);
     try {
         const std::string cmd = argc > 1 ? argv[1] : "";
-        if (cmd == "build" && argc == 7) return build(argv + 2);
+        if (cmd == "build" && (argc == 7 || argc == 8)) return build(argv + 2);  // (argv[argc] is null)
+        if (cmd == "coarse" && argc == 9) return coarse(argv + 2);
         if (cmd == "run" && argc == 8) return run(argv + 2);
         fprintf(stderr, "usage: see the head of hnsw_params_driver.cpp\n");
         return 2;
