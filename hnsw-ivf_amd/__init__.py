@@ -255,6 +255,21 @@ def _declare(L):
         "faiss_Index_reconstruct": (C.c_int, [_P, _I64, _P]),
         "faiss_Index_reconstruct_n": (C.c_int, [_P, _I64, _I64, _P]),
         "faiss_Index_assign": (C.c_int, [_P, _I64, _P, _P, _I64]),
+        "faiss_Index_remove_ids": (C.c_int, [_P, _P, C.POINTER(C.c_size_t)]),
+        "faiss_IDSelectorArray_new": (C.c_int, [C.POINTER(_P), C.c_size_t, _P]),
+        "faiss_IndexIVF_make_direct_map": (C.c_int, [_P, C.c_int]),
+        "faiss_amd_IndexIVF_set_direct_map_type": (C.c_int, [_P, C.c_int]),
+        "faiss_amd_IndexIVF_direct_map_type": (C.c_int, [_P]),
+        "faiss_amd_IndexIVF_direct_map_get": (C.c_int, [_P, _I64, C.POINTER(C.c_int64)]),
+        "faiss_amd_IndexIVF_update_vectors": (C.c_int, [_P, C.c_int, _P, _P]),
+        "faiss_IndexIVFFlat_update_vectors": (C.c_int, [_P, C.c_int, _P, _P]),
+        "faiss_amd_IndexIVF_reconstruct_from_offset": (C.c_int, [_P, _I64, _I64, _P]),
+        "faiss_amd_IndexIVF_materialize_invlists": (C.c_int, [_P]),
+        "faiss_amd_IndexIVFPQ_set_by_residual": (C.c_int, [_P, C.c_int]),
+        "faiss_amd_IndexIVF_reconstruct_pairs_device": (C.c_int, [_P, _I64, _P, _P, _P]),
+        "faiss_amd_IndexIVF_search_and_reconstruct": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P, _P]),
+        "faiss_amd_IndexIVF_search_and_reconstruct_device": (C.c_int, [_P, _I64, _P, _I64, _P, _P,
+                                                                       _P, _P, _P]),
         "faiss_IndexIVF_imbalance_factor": (C.c_double, [_P]),
         "faiss_IndexRefineFlat_new": (C.c_int, [C.POINTER(_P), _P]),
         "faiss_IndexRefineFlat_own_fields": (C.c_int, [_P]),
@@ -382,6 +397,33 @@ class Index:
 
     def reset(self):
         _check(lib().faiss_Index_reset(self.h))
+
+    def remove_ids(self, sel):
+        """faiss Index.remove_ids: sel is an IDSelector or an array of ids (an
+        IDSelectorArray, removed in the array's order).  Returns the count.
+        IndexFlat asks the selector about row numbers; index types without
+        removal raise the reference's message."""
+        if not isinstance(sel, IDSelector):
+            sel = IDSelectorArray(sel)
+        n = C.c_size_t(0)
+        _check(lib().faiss_Index_remove_ids(self.h, sel.h, C.byref(n)))
+        return n.value
+
+    def reconstruct(self, key):
+        """faiss Index.reconstruct: the stored (decoded) vector of id key."""
+        out = np.empty(self.d, dtype=np.float32)
+        _check(lib().faiss_Index_reconstruct(self.h, int(key), _ptr(out)))
+        return out
+
+    def reconstruct_n(self, i0, ni, out=None):
+        """faiss Index.reconstruct_n: [ni][d].  On an IndexIVF ids of the range
+        that are not stored leave their rows of `out` as they were (a fresh
+        buffer is zeroed)."""
+        if out is None:
+            out = np.zeros((int(ni), self.d), dtype=np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == ni * self.d
+        _check(lib().faiss_Index_reconstruct_n(self.h, int(i0), int(ni), _ptr(out)))
+        return out
 
     # ---- device-resident extensions (pointers are ints, e.g. tensor.data_ptr())
     def sync_device(self):
@@ -570,6 +612,73 @@ class IndexIVF(Index):
     def get_list_size(self, l):
         return lib().faiss_IndexIVF_get_list_size(self.h, l)
 
+    # ---- direct map (faiss/invlists/DirectMap.h), mutation, reconstruction
+    def make_direct_map(self, new_maintain_direct_map=True):
+        _check(lib().faiss_IndexIVF_make_direct_map(self.h, int(bool(new_maintain_direct_map))))
+
+    def set_direct_map_type(self, type):
+        """DIRECT_MAP_NONE / DIRECT_MAP_ARRAY / DIRECT_MAP_HASHTABLE."""
+        _check(lib().faiss_amd_IndexIVF_set_direct_map_type(self.h, int(type)))
+
+    @property
+    def direct_map_type(self):
+        t = lib().faiss_amd_IndexIVF_direct_map_type(self.h)
+        if t < 0:
+            _check(-2)
+        return t
+
+    def direct_map_get(self, key):
+        """(list_no, offset) of id key; raises the reference's messages."""
+        lo = C.c_int64(0)
+        _check(lib().faiss_amd_IndexIVF_direct_map_get(self.h, int(key), C.byref(lo)))
+        return lo.value >> 32, lo.value & 0xffffffff
+
+    def update_vectors(self, ids, x):
+        """faiss IndexIVF.update_vectors: new vectors x for the stored ids."""
+        x = _f32(x)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        assert len(ids) == x.shape[0]
+        _check(lib().faiss_amd_IndexIVF_update_vectors(self.h, len(ids), _ptr(ids), _ptr(x)))
+
+    def materialize_invlists(self):
+        """Copy lists mapped from a file (IO_FLAG_MMAP) to host memory, so the
+        index can be edited."""
+        _check(lib().faiss_amd_IndexIVF_materialize_invlists(self.h))
+
+    def reconstruct_from_offset(self, list_no, offset):
+        out = np.empty(self.d, dtype=np.float32)
+        _check(lib().faiss_amd_IndexIVF_reconstruct_from_offset(self.h, int(list_no),
+                                                                int(offset), _ptr(out)))
+        return out
+
+    def search_and_reconstruct(self, xq, k, params=None):
+        """faiss IndexIVF.search_and_reconstruct: (D [n][k], I [n][k],
+        recons [n][k][d]); a slot without a result has I = -1 and d words of
+        0xFFFFFFFF (NaN) in recons.  The rows are gathered and decoded on the GPU."""
+        x = _f32(xq)
+        n = x.shape[0]
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.int64)
+        R = np.empty((n, k, self.d), dtype=np.float32)
+        _check(lib().faiss_amd_IndexIVF_search_and_reconstruct(
+            self.h, n, _ptr(x), k, params.h if params is not None else None, _ptr(D), _ptr(I),
+            _ptr(R)))
+        return D, I, R
+
+    def reconstruct_pairs_device(self, n, labels_ptr, R_ptr, stream=None):
+        """The gather-and-decode kernel alone: labels [n] (device, int64) hold
+        (list << 32) | offset pairs or negative values and become ids, R [n][d]
+        (device) the decoded rows."""
+        _check(lib().faiss_amd_IndexIVF_reconstruct_pairs_device(
+            self.h, n, C.c_void_p(labels_ptr), C.c_void_p(R_ptr), C.c_void_p(stream or 0)))
+
+    def search_and_reconstruct_device(self, n, x_ptr, k, D_ptr, I_ptr, R_ptr, stream=None,
+                                      params=None):
+        """Device pointers (ints); recons stays in HBM."""
+        _check(lib().faiss_amd_IndexIVF_search_and_reconstruct_device(
+            self.h, n, C.c_void_p(x_ptr), k, params.h if params is not None else None,
+            C.c_void_p(D_ptr), C.c_void_p(I_ptr), C.c_void_p(R_ptr), C.c_void_p(stream or 0)))
+
     def list_ids(self, l):
         n = self.get_list_size(l)
         out = np.empty(n, dtype=np.int64)
@@ -719,6 +828,15 @@ class IndexIVFPQ(IndexIVF):
         _check(lib().faiss_amd_IndexIVFPQ_set_use_precomputed_table(self.h, int(v)))
 
     @property
+    def by_residual(self):
+        return self.pq_info()["by_residual"]
+
+    @by_residual.setter
+    def by_residual(self, v):
+        """On an empty index: codes added afterwards encode x, not x - centroid."""
+        _check(lib().faiss_amd_IndexIVFPQ_set_by_residual(self.h, int(bool(v))))
+
+    @property
     def pq_centroids(self):
         p = C.POINTER(C.c_float)()
         n = C.c_size_t(0)
@@ -836,6 +954,9 @@ class IndexShardsIVF(IndexIVF):
         s = C.c_void_p()
         _check(lib().faiss_amd_IndexShardsIVF_shard(self.h, i, C.byref(s)))
         return _wrap(s, owner=self)
+
+
+DIRECT_MAP_NONE, DIRECT_MAP_ARRAY, DIRECT_MAP_HASHTABLE = 0, 1, 2
 
 
 class IDSelector:

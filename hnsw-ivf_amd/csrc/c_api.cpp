@@ -134,8 +134,63 @@ int faiss_Index_reconstruct(const FaissIndex* index, idx_t key, float* recons) {
 }
 // faiss/Index.cpp:50-55
 int faiss_Index_reconstruct_n(const FaissIndex* index, idx_t i0, idx_t ni, float* recons) {
-    C_TRY const Index* ix = IX(index);
-    for (idx_t i = 0; i < ni; i++) ix->reconstruct(i0 + i, recons + (size_t)i * ix->d);
+    C_TRY IX(index)->reconstruct_n(i0, ni, recons);
+    C_CATCH
+}
+// c_api/Index_c.h:174-181
+int faiss_Index_remove_ids(FaissIndex* index, const FaissIDSelector* sel, size_t* n_removed) {
+    C_TRY FAISS_THROW_IF_NOT_MSG(sel, "remove_ids: no selector");
+    const size_t n = IX(index)->remove_ids(*reinterpret_cast<const IDSelector*>(sel));
+    if (n_removed) *n_removed = n;
+    C_CATCH
+}
+// c_api/IndexIVF_c.h:125-132
+int faiss_IndexIVF_make_direct_map(FaissIndexIVF* index, int new_maintain_direct_map) {
+    C_TRY IVF(index)->make_direct_map(new_maintain_direct_map != 0);
+    C_CATCH
+}
+int faiss_amd_IndexIVF_set_direct_map_type(FaissIndexIVF* index, int type) {
+    C_TRY FAISS_THROW_IF_NOT_FMT(type >= 0 && type <= 2, "direct map type %d is not known", type);
+    IVF(index)->set_direct_map_type((DirectMap::Type)type);
+    C_CATCH
+}
+// the type (0, 1, 2), or -1 with the message set when index is no IndexIVF
+int faiss_amd_IndexIVF_direct_map_type(const FaissIndexIVF* index) {
+    try {
+        return (int)IVF(index)->direct_map().type;
+    } catch (std::exception& e) {
+        g_last_error = e.what();
+    } catch (...) {
+        g_last_error = "Unknown error";
+    }
+    return -1;
+}
+// entry of id in the direct map (lo_build(list, offset)); -2 with the message set
+int faiss_amd_IndexIVF_direct_map_get(const FaissIndexIVF* index, idx_t id, idx_t* lo) {
+    C_TRY* lo = IVF(index)->direct_map().get(id);
+    C_CATCH
+}
+int faiss_amd_IndexIVF_update_vectors(FaissIndexIVF* index, int nv, const idx_t* idx,
+                                      const float* v) {
+    C_TRY IVF(index)->update_vectors(nv, idx, v);
+    C_CATCH
+}
+// c_api/IndexIVFFlat_c.h:67-79
+int faiss_IndexIVFFlat_update_vectors(FaissIndexIVFFlat* index, int nv, idx_t* idx,
+                                      const float* v) {
+    C_TRY auto fl = dynamic_cast<IndexIVFFlat*>(IX(index));
+    FAISS_THROW_IF_NOT_MSG(fl, "index is not an IndexIVFFlat");
+    fl->update_vectors(nv, idx, v);
+    C_CATCH
+}
+// copy lists mapped from a file into host memory (they can then be edited)
+int faiss_amd_IndexIVF_materialize_invlists(FaissIndexIVF* index) {
+    C_TRY IVF(index)->invlists->materialize();
+    C_CATCH
+}
+int faiss_amd_IndexIVF_reconstruct_from_offset(const FaissIndexIVF* index, int64_t list_no,
+                                               int64_t offset, float* recons) {
+    C_TRY IVF(index)->reconstruct_from_offset(list_no, offset, recons);
     C_CATCH
 }
 
@@ -193,6 +248,9 @@ int faiss_IDSelectorBatch_new(FaissIDSelectorBatch** p_sel, size_t n, const idx_
 int faiss_amd_IDSelectorArray_new(FaissIDSelector** p_sel, size_t n, const idx_t* ids) {
     C_TRY* p_sel = reinterpret_cast<FaissIDSelector*>(new IDSelectorArray(n, ids));
     C_CATCH
+}
+int faiss_IDSelectorArray_new(FaissIDSelector** p_sel, size_t n, const idx_t* ids) {
+    return faiss_amd_IDSelectorArray_new(p_sel, n, ids);
 }
 int faiss_IDSelectorBitmap_new(FaissIDSelectorBitmap** p_sel, size_t n, const uint8_t* bitmap) {
     C_TRY* p_sel = reinterpret_cast<FaissIDSelectorBitmap*>(new IDSelectorBitmap(n, bitmap));
@@ -573,6 +631,16 @@ int faiss_amd_IndexIVFPQ_info(const FaissIndexIVFPQ* index, size_t* M, size_t* n
     *nbits = pq->pq.nbits;
     *by_residual = pq->by_residual ? 1 : 0;
     *use_precomputed_table = pq->use_precomputed_table;
+    C_CATCH
+}
+// IndexIVFPQ::by_residual (faiss/IndexIVF.h:181), to be set before train / add:
+// the codes stored afterwards encode the vectors themselves
+int faiss_amd_IndexIVFPQ_set_by_residual(FaissIndexIVFPQ* index, int v) {
+    C_TRY auto pq = dynamic_cast<IndexIVFPQ*>(IX(index));
+    FAISS_THROW_IF_NOT_MSG(pq, "index is not an IndexIVFPQ");
+    FAISS_THROW_IF_NOT_MSG(pq->ntotal == 0, "by_residual is set on an empty index");
+    pq->by_residual = v != 0;
+    pq->precompute_table();
     C_CATCH
 }
 int faiss_amd_IndexIVFPQ_set_use_precomputed_table(FaissIndexIVFPQ* index, int v) {
@@ -1023,6 +1091,35 @@ int faiss_amd_IndexIVF_search_preassigned_device(const FaissIndexIVF* index, idx
     ix->sync_device();
     ix->search_preassigned_device_ordered(n, x_dev, ldx_of(ix), k, nprobe, assign_dev, cdis_dev,
                                           d_dev, l_dev, pick_stream(ix, stream));
+    C_CATCH
+}
+int faiss_amd_IndexIVF_search_and_reconstruct(const FaissIndexIVF* index, idx_t n, const float* x,
+                                              idx_t k, const FaissSearchParameters* params,
+                                              float* distances, idx_t* labels, float* recons) {
+    C_TRY IVF(index)->search_and_reconstruct(n, x, k, distances, labels, recons,
+                                             resolve_params(params));
+    C_CATCH
+}
+// the kernel alone: labels [n] hold lo_build(list, offset) pairs (or < 0) and
+// become the stored ids, recons [n][d] the decoded rows (device pointers)
+int faiss_amd_IndexIVF_reconstruct_pairs_device(const FaissIndexIVF* index, idx_t n,
+                                                idx_t* labels_dev, float* recons_dev,
+                                                void* stream) {
+    C_TRY const IndexIVF* ix = IVF(index);
+    ensure_hip();
+    ix->reconstruct_pairs_device(n, labels_dev, recons_dev, pick_stream(ix, stream));
+    C_CATCH
+}
+int faiss_amd_IndexIVF_search_and_reconstruct_device(const FaissIndexIVF* index, idx_t n,
+                                                     const float* x_dev, idx_t k,
+                                                     const FaissSearchParameters* params,
+                                                     float* d_dev, idx_t* l_dev,
+                                                     float* recons_dev, void* stream) {
+    C_TRY const IndexIVF* ix = IVF(index);
+    FAISS_THROW_IF_NOT_MSG(ix->d % 4 == 0, "device entry points need d % 4 == 0");
+    ensure_hip();
+    ix->search_and_reconstruct_device(n, x_dev, ldx_of(ix), k, d_dev, l_dev, recons_dev,
+                                      resolve_params(params), pick_stream(ix, stream));
     C_CATCH
 }
 int faiss_amd_IndexIVF_quantize_device(const FaissIndexIVF* index, idx_t n, const float* x_dev,

@@ -6,7 +6,8 @@
 //             [metric_arg:f32 if metric > 1]                 (write :79-90)
 //   IxF2/IxFI = header, size_t n4, n4*4 bytes of floats       (:396-403)
 //   IVF hdr = header, nlist:size_t, nprobe:size_t, nested quantizer,
-//             direct map (char type, vector<idx_t>)           (:367-389)
+//             direct map (char type, vector<idx_t> array, and for a
+//             Hashtable vector<(idx_t id, idx_t entry)>)        (:367-389)
 //   IwFl    = IVF hdr, invlists                               (:631-638)
 //   IwPQ    = IVF hdr, by_residual:u8, code_size:size_t, PQ (d,M,nbits:size_t,
 //             vector<float> centroids), invlists               (:697-705,155-160)
@@ -28,6 +29,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <cstdlib>
 #include <cstring>
@@ -443,9 +445,17 @@ void write_ivf_header(const IndexIVF* ivf, Writer& w) {
     w.one<size_t>(ivf->nlist);
     w.one<size_t>(ivf->nprobe);
     write_index_impl(ivf->quantizer, w);
-    w.one<char>(0);  // DirectMap::NoMap
-    std::vector<idx_t> empty;
-    w.vec(empty);
+    // faiss/impl/index_write.cpp:367-380: the type, the array, and for a
+    // Hashtable its (id, entry) pairs — in ascending id order here (the
+    // reference writes its unordered_map's iteration order)
+    const DirectMap& dm = ivf->direct_map();
+    w.one<char>((char)dm.type);
+    w.vec(dm.array);
+    if (dm.type == DirectMap::Hashtable) {
+        std::vector<std::pair<idx_t, idx_t>> v(dm.hashtable.begin(), dm.hashtable.end());
+        std::sort(v.begin(), v.end());
+        w.vec(v);
+    }
 }
 
 void write_index_impl(const Index* idx, Writer& w) {
@@ -554,10 +564,20 @@ Index* read_index_impl(Reader& r, int io_flags) {
         size_t nprobe = r.one<size_t>();
         Index* q = read_index_impl(r, io_flags);
         FAISS_THROW_IF_NOT_MSG(q, "IVF index without quantizer");
-        char dm = r.one<char>();
-        std::vector<idx_t> dmarr;
-        r.vec(dmarr);
-        FAISS_THROW_IF_NOT_MSG(dm == 0, "direct maps are not supported");
+        // faiss/impl/index_read.cpp:286-301
+        DirectMap dmap;
+        const char dm = r.one<char>();
+        FAISS_THROW_IF_NOT_FMT(dm == DirectMap::NoMap || dm == DirectMap::Array ||
+                                       dm == DirectMap::Hashtable,
+                               "direct map type %d is not known", (int)dm);
+        dmap.type = (DirectMap::Type)dm;
+        r.vec(dmap.array);
+        if (dmap.type == DirectMap::Hashtable) {
+            std::vector<std::pair<idx_t, idx_t>> v;
+            r.vec(v);
+            dmap.hashtable.reserve(v.size());
+            for (const auto& e : v) dmap.hashtable[e.first] = e.second;
+        }
         IndexIVF* ivf;
         if (h == fourcc("IwFl")) {
             ivf = new IndexIVFFlat(q, hd.d, nlist, (MetricType)hd.metric);
@@ -603,6 +623,7 @@ Index* read_index_impl(Reader& r, int io_flags) {
         ivf->own_fields = true;
         apply_header(ivf, hd);
         ivf->nprobe = nprobe;
+        ivf->direct_map() = std::move(dmap);
         read_invlists(ivf->invlists.get(), r, nlist, ivf->code_size, io_flags);
         if (auto pqi = dynamic_cast<IndexIVFPQ*>(ivf)) {
             // faiss/impl/index_read.cpp:510-516

@@ -157,24 +157,40 @@ void IndexIVF::add(idx_t n, const float* x) { add_with_ids(n, x, nullptr); }
 
 void IndexIVF::add_with_ids(idx_t n, const float* x, const idx_t* xids) {
     FAISS_THROW_IF_NOT(is_trained);
+    direct_map().check_can_add(xids);
     const idx_t bs = 1 << 20;
     std::vector<idx_t> assign;
     std::vector<float> dis;
-    std::vector<uint8_t> codes;
     for (idx_t i0 = 0; i0 < n; i0 += bs) {
         idx_t nb = std::min(bs, n - i0);
         assign.resize(nb);
         dis.resize(nb);
-        codes.resize((size_t)nb * code_size);
         const float* xb = x + (size_t)i0 * d;
         quantizer->search(nb, xb, 1, dis.data(), assign.data());
-        encode_vectors(nb, xb, assign.data(), codes.data());
-        for (idx_t i = 0; i < nb; i++) {
-            idx_t l = assign[i];
-            if (l < 0) continue;
-            idx_t id = xids ? xids[i0 + i] : ntotal + i0 + i;
-            invlists->add_entries(l, 1, &id, codes.data() + (size_t)i * code_size);
+        add_core(nb, xb, xids ? xids + i0 : nullptr, assign.data());
+    }
+}
+
+// faiss/IndexIVF.cpp:211-285 on one thread: entries in the order of x, the
+// direct map told of each (a vector without a list: -1 in an Array map, no
+// Hashtable entry)
+void IndexIVF::add_core(idx_t n, const float* x, const idx_t* xids, const idx_t* coarse_idx) {
+    FAISS_THROW_IF_NOT(coarse_idx);
+    FAISS_THROW_IF_NOT(is_trained);
+    direct_map().check_can_add(xids);
+    if (!direct_map().no()) invlists->check_not_mapped("an add that maintains a direct map");
+    std::vector<uint8_t> codes((size_t)n * code_size);
+    encode_vectors(n, x, coarse_idx, codes.data());
+    for (idx_t i = 0; i < n; i++) {
+        const idx_t l = coarse_idx[i];
+        const idx_t id = xids ? xids[i] : ntotal + i;
+        if (l < 0) {
+            direct_map().add_single_id(id, -1, 0);
+            continue;
         }
+        const size_t ofs = invlists->list_size(l);
+        invlists->add_entries(l, 1, &id, codes.data() + (size_t)i * code_size);
+        direct_map().add_single_id(id, l, ofs);
     }
     ntotal += n;
     std::lock_guard<std::recursive_mutex> g(mu_);
@@ -182,6 +198,7 @@ void IndexIVF::add_with_ids(idx_t n, const float* x, const idx_t* xids) {
 }
 
 void IndexIVF::reset() {
+    direct_map().clear();
     invlists->reset();
     ntotal = 0;
     std::lock_guard<std::recursive_mutex> g(mu_);
@@ -1321,6 +1338,10 @@ void IndexIVFFlat::encode_vectors(idx_t n, const float* x, const idx_t*, uint8_t
 }
 
 void IndexIVFFlat::reconstruct(idx_t key, float* recons) const {
+    if (!direct_map().no()) {
+        IndexIVF::reconstruct(key, recons);
+        return;
+    }
     for (size_t l = 0; l < nlist; l++) {
         const idx_t* ids = invlists->get_ids(l);
         for (size_t i = 0; i < invlists->list_size(l); i++)
@@ -2041,7 +2062,7 @@ void ScalarQuantizer::decode(const uint8_t* codes, float* x, size_t n) const {
     const float *vmin = trained.data(), *vdiff = trained.data() + d;
     for (size_t i = 0; i < n; i++)
         for (size_t j = 0; j < d; j++)
-            x[i * d + j] = kern::sq_recons8(codes[i * d + j], vmin[j], vdiff[j]);
+            x[i * d + j] = kern::sq_decode_vector8(codes[i * d + j], vmin[j], vdiff[j]);
 }
 
 IndexIVFScalarQuantizer::IndexIVFScalarQuantizer(Index* q, size_t d_, size_t nl,
@@ -2104,16 +2125,7 @@ void IndexIVFScalarQuantizer::add_core(idx_t n, const float* x, const idx_t* xid
     for (idx_t i = 0; i < n; i++)
         FAISS_THROW_IF_NOT_FMT(precomputed_idx[i] < (idx_t)nlist, "Invalid key=%lld nlist=%zd",
                                (long long)precomputed_idx[i], nlist);
-    std::vector<uint8_t> codes((size_t)n * code_size);
-    encode_vectors(n, x, precomputed_idx, codes.data());
-    for (idx_t i = 0; i < n; i++) {
-        if (precomputed_idx[i] < 0) continue;
-        const idx_t id = xids ? xids[i] : ntotal + i;
-        invlists->add_entries(precomputed_idx[i], 1, &id, codes.data() + (size_t)i * code_size);
-    }
-    ntotal += n;
-    std::lock_guard<std::recursive_mutex> g(mu_);
-    dirty_ = true;
+    IndexIVF::add_core(n, x, xids, precomputed_idx);
 }
 
 void IndexIVFScalarQuantizer::upload_extra() const {

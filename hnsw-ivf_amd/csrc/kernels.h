@@ -284,6 +284,29 @@ int64_t ivf_exact_chunk(int64_t n, int np, uint32_t max_list_len, int64_t* cap_o
 // eoff [n*np], total [n], keys / rows [n*cap] scratch
 void ivf_exact_search(const ExactScanArgs& a, uint32_t* eoff, uint32_t* total, uint32_t* keys,
                       uint32_t* rows, int64_t cap, float* D, int64_t* I, hipStream_t s);
+// ---------------- result rows decoded (kernels_reconstruct.hip) ----------------
+constexpr int RECONS_FLAT = 0, RECONS_PQ = 1, RECONS_SQ8 = 2, RECONS_SQFP16 = 3;
+struct ReconsArgs {
+    int kind = RECONS_FLAT;
+    int d = 0;
+    int by_residual = 0;
+    const uint8_t* codes = nullptr;  // arena rows
+    int stride = 0;                  // bytes of a row's slot (multiple of 4)
+    const int64_t* ids = nullptr;    // id of each arena row
+    const uint32_t* list_off = nullptr;
+    const uint32_t* list_len = nullptr;
+    int nlist = 0;
+    const float* cent = nullptr;  // coarse centroids [nlist][ldcent] (by_residual)
+    int ldcent = 0;
+    const float* pq_cent = nullptr;  // [M][1 << nbits][dsub]
+    int M = 0, dsub = 0, nbits = 8;
+    const float* trained = nullptr;  // SQ8: vmin [d] | vdiff [d]
+};
+// labels [n]: lo_build(list, offset) pairs, or < 0.  Each pair becomes the
+// stored id and recons[i][0..d) the decoded row (+ the list's centroid when
+// by_residual); a negative label stays and its row is d words of 0xFFFFFFFF
+void ivf_reconstruct_pairs(const ReconsArgs& a, int64_t n, int64_t* labels, float* recons,
+                           hipStream_t s);
 // IVF-PQ range scan of any geometry / metric (same contract as ivfpq_range;
 // a.x / a.assign / a.cdis / a.sel / a.ids / a.row_list / a.store_pairs used)
 void ivfpq_range_exact(const ExactScanArgs& a, float radius, uint32_t* counts,

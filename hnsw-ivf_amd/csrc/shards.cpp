@@ -59,6 +59,10 @@ size_t ivf_copy_subset_to(const IndexIVF* src, IndexIVF* dst, int subset_type, i
     FAISS_THROW_IF_NOT_MSG(!dynamic_cast<const IndexIVFScalarQuantizer*>(src) &&
                                    !dynamic_cast<const IndexIVFScalarQuantizer*>(dst),
                            "copy_subset_to is not supported on IndexIVFScalarQuantizer");
+    // (the reference appends to the lists and leaves such a map stale)
+    FAISS_THROW_IF_NOT_MSG(dst->direct_map().no(),
+                           "copy_subset_to: the destination has a direct map, which the copy "
+                           "would not maintain (set_direct_map_type(NoMap) first)");
     const ArrayInvertedLists& il = *src->invlists;
     ArrayInvertedLists& ol = *dst->invlists;
     FAISS_THROW_IF_NOT(il.nlist == ol.nlist);
@@ -182,6 +186,11 @@ IndexShardsIVF* index_ivf_to_shards(const IndexIVF* src, int nshard, int shard_t
                            "index_ivf_to_shards is not supported on IndexIVFScalarQuantizer");
     FAISS_THROW_IF_NOT_FMT(shard_type == 1 || shard_type == 2 || shard_type == 4,
                            "shard_type %d not implemented", shard_type);
+    // (a shard is a copy of src through the file format, its direct map included)
+    FAISS_THROW_IF_NOT_MSG(src->direct_map().no(),
+                           "index_ivf_to_shards: the index has a direct map, which the shards "
+                           "would carry without maintaining it (set_direct_map_type(NoMap) "
+                           "first)");
     std::vector<IndexIVF*> sh;
     try {
         for (int i = 0; i < nshard; i++) {

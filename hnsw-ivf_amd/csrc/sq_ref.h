@@ -39,6 +39,20 @@ SQ_HD float sq_decode8(uint8_t c) { return fmaf((float)c, 1.f / 255.f, 0.5f / 25
 SQ_HD float sq_recons8(uint8_t c, float vmin, float vdiff) {
     return fmaf(sq_decode8(c), vdiff, vmin);
 }
+// ScalarQuantizer::decode (QuantizerTemplate<.., NON_UNIFORM, 1>::decode_vector,
+// :500-505, Codec8bit::decode_component :87-89) is not the scanner's form: the
+// component is a true division, xi = (code + 0.5f) / 255.0f, and the
+// reference's compiler contracts vmin + xi * vdiff into one fma.  Settled by
+// the reference's output for all 256 codes (tests/golden/ref_mutation.npz
+// sq_decode: 1144 of 2048 values differ from sq_recons8).
+SQ_HD float sq_decode_vector8(uint8_t c, float vmin, float vdiff) {
+#ifdef __HIP_DEVICE_COMPILE__
+    const float xi = __fdiv_rn((float)c + 0.5f, 255.0f);
+#else
+    const float xi = ((float)c + 0.5f) / 255.0f;
+#endif
+    return fmaf(xi, vdiff, vmin);
+}
 SQ_HD float sq_half_to_float(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
 SQ_HD uint16_t sq_float_to_half(float x) {  // round to nearest even
     return __builtin_bit_cast(uint16_t, (_Float16)x);

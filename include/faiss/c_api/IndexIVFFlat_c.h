@@ -2,7 +2,7 @@
  * IndexIVFFlat_c.h — drop-in for the reference C API header `c_api/IndexIVFFlat_c.h`
  * (Quaternijkon/hnsw-ivf = Faiss 1.10.0).  A C caller of the reference keeps
  * its `#include "IndexIVFFlat_c.h"` (or <faiss/c_api/IndexIVFFlat_c.h>) and links
- * libfaiss_amd.so: the declarations — IndexIVFFlat constructors, cast, destructor and getters —
+ * libfaiss_amd.so: the declarations — IndexIVFFlat constructors, cast, destructor, getters and update_vectors —
  * are this library's, with the reference's names, signatures and return codes
  * (include/faiss_amd_c.h, which cites each reference declaration).
  */

@@ -66,6 +66,12 @@ using faiss_amd::SUBSET_TYPE_ID_RANGE;
 using faiss_amd::SUBSET_TYPE_INVLIST;
 using faiss_amd::SUBSET_TYPE_INVLIST_FRACTION;
 
+// faiss/invlists/DirectMap.h
+using faiss_amd::DirectMap;
+using faiss_amd::lo_build;
+using faiss_amd::lo_listno;
+using faiss_amd::lo_offset;
+
 // faiss/IndexIVF.h (this fork's QueryLatencyStats and search_stats included)
 using faiss_amd::IndexIVF;
 using faiss_amd::indexIVF_stats;

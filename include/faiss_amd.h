@@ -19,6 +19,7 @@
 #include <mutex>
 #include <random>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../hnsw-ivf_amd/csrc/common.h"
@@ -249,6 +250,17 @@ struct Index {
     // per-rank quantizers, and captured search graphs are rebuilt when it
     // moves); atomic: searches on other threads read it without the lock
     virtual uint64_t content_version() const { return version_.load(); }
+    // (declared after the virtuals above: the slots of Index's own virtuals
+    // — destructor, train, add, search, reset, ... — do not move.  The
+    // virtuals that derived classes introduce, e.g. IndexIVF::train_encoder,
+    // do move down by these two entries)
+    // faiss/Index.cpp:70-75: reconstruct(i0 + i) for i in [0, ni); IndexIVF
+    // makes one pass over its lists instead
+    virtual void reconstruct_n(idx_t i0, idx_t ni, float* recons) const;
+    // faiss/Index.h:216-218: remove the members of sel, return how many went.
+    // The base version throws (faiss/Index.cpp:48); IndexFlat and IndexIVF
+    // implement it
+    virtual size_t remove_ids(const IDSelector& sel);
 
     hipStream_t stream() const;
     int ld() const { return (int)roundup((size_t)d, 4); }
@@ -279,6 +291,9 @@ struct IndexFlat : Index {
                        hipStream_t stream) const override;
     void reset() override;
     void reconstruct(idx_t key, float* recons) const override;
+    // faiss/IndexFlatCodes.cpp:53-73: sel is asked about row numbers; the
+    // surviving rows keep their order
+    size_t remove_ids(const IDSelector& sel) override;
     void sync_device() const override;
     // faiss/IndexFlat.cpp:71-90: hits of a query in ascending row order; the
     // BLAS form for >= 20 queries without a selector, else the direct form
@@ -488,6 +503,33 @@ struct MappedFile {
     ~MappedFile();
 };
 
+// faiss/invlists/InvertedLists.h:21-33: (list, offset) packed in one idx_t
+inline idx_t lo_build(idx_t list_id, idx_t offset) { return (list_id << 32) | offset; }
+inline idx_t lo_listno(idx_t lo) { return lo >> 32; }
+inline idx_t lo_offset(idx_t lo) { return lo & 0xffffffff; }
+
+// faiss/invlists/DirectMap.h:27-89: id -> lo_build(list, offset) of an
+// IndexIVF.  Array needs the ids 0 .. ntotal - 1; Hashtable takes any ids.
+struct ArrayInvertedLists;
+struct DirectMap {
+    enum Type { NoMap = 0, Array = 1, Hashtable = 2 };
+    Type type = NoMap;
+    std::vector<idx_t> array;
+    std::unordered_map<idx_t, idx_t> hashtable;
+
+    void set_type(Type new_type, const ArrayInvertedLists* invlists, size_t ntotal);
+    idx_t get(idx_t id) const;  // throws when the id has no entry
+    bool no() const { return type == NoMap; }
+    void check_can_add(const idx_t* ids);
+    void add_single_id(idx_t id, idx_t list_no, size_t offset);
+    void clear();  // the contents; the type stays
+    // faiss/invlists/DirectMap.cpp:147-221
+    size_t remove_ids(const IDSelector& sel, ArrayInvertedLists* invlists);
+    // faiss/invlists/DirectMap.cpp:223-258 (Array only)
+    void update_codes(ArrayInvertedLists* invlists, int n, const idx_t* ids, const idx_t* list_nos,
+                      const uint8_t* codes);
+};
+
 // faiss/invlists/InvertedLists.h:37-275 (ArrayInvertedLists) with the
 // OnDiskInvertedLists read-only case folded in: a list lives either in host
 // vectors (codes[l], ids[l]) or, when `map` is set, in the mapped file
@@ -508,6 +550,10 @@ struct ArrayInvertedLists {
     // free-slot table (offset, capacity), written back verbatim
     std::vector<size_t> ondisk_lists, ondisk_slots;
     size_t ondisk_totsize = 0;
+    // the owning IndexIVF's direct map (IndexIVF::direct_map()): kept with the
+    // lists it indexes, so sizeof and the member offsets of the index classes
+    // are what they were (this struct itself grows: 216 -> 304 bytes)
+    DirectMap direct_map;
     ArrayInvertedLists(size_t nlist, size_t code_size);
     bool is_mapped() const { return (bool)map; }
     size_t list_size(size_t l) const { return map ? map_sizes[l] : ids[l].size(); }
@@ -516,6 +562,11 @@ struct ArrayInvertedLists {
     void materialize();  // copy mapped lists into host vectors and drop the mapping
     void add_entries(size_t l, size_t n, const idx_t* ids, const uint8_t* codes);
     void reset();
+    // faiss/invlists/InvertedLists.cpp:330-350 (update_entry, resize) on host
+    // lists; a mapped set throws, naming the mapping (materialize() first)
+    void update_entry(size_t l, size_t offset, idx_t id, const uint8_t* code);
+    void resize(size_t l, size_t new_size);
+    void check_not_mapped(const char* what) const;
 };
 
 struct IndexIVF;
@@ -609,6 +660,40 @@ struct IndexIVF : Index {
     void reset() override;
     void sync_device() const override;
 
+    // the reference's IndexIVF::direct_map, kept up to date by every add,
+    // remove and update.  A method, not a field: the map is stored with the
+    // lists (invlists->direct_map), see there
+    DirectMap& direct_map() { return invlists->direct_map; }
+    const DirectMap& direct_map() const { return invlists->direct_map; }
+    // faiss/IndexIVF.cpp:287-297: (re)build the direct map from the lists
+    void make_direct_map(bool new_maintain_direct_map = true);
+    void set_direct_map_type(DirectMap::Type type);
+    // faiss/IndexIVF.cpp:211-285: add to the lists coarse_idx names (< 0: the
+    // vector is stored nowhere; it still takes an id)
+    void add_core(idx_t n, const float* x, const idx_t* xids, const idx_t* coarse_idx);
+    // faiss/IndexIVF.cpp:1594 + DirectMap::remove_ids.  The order left in a
+    // list is the reference's (the last entry moves into a removed slot)
+    size_t remove_ids(const IDSelector& sel) override;
+    // faiss/IndexIVF.cpp:1600-1624: replace the vectors of n stored ids
+    // (Hashtable: remove then add; Array: in place; no map: throws)
+    void update_vectors(int n, const idx_t* ids, const float* x);
+    // faiss/IndexIVF.cpp:1407-1429: through the direct map / one pass over
+    // the lists (ids of the range that are absent leave their rows untouched)
+    void reconstruct(idx_t key, float* recons) const override;
+    void reconstruct_n(idx_t i0, idx_t ni, float* recons) const override;
+    // faiss/IndexIVF.cpp:1459-1512: search with store_pairs, then per result
+    // slot the stored id and the decoded vector (recons [n][k][d]); a slot
+    // without a result keeps label -1 and gets d words of 0xFFFFFFFF.  The
+    // gather and decode is kern::ivf_reconstruct_pairs on the HBM arena
+    void search_and_reconstruct(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels,
+                                float* recons, const SearchParameters* params = nullptr) const;
+    // device pointers (x rows of leading dimension ldx; recons stays in HBM)
+    void search_and_reconstruct_device(idx_t n, const float* x, int ldx, idx_t k,
+                                       float* distances, idx_t* labels, float* recons,
+                                       const SearchParameters* params, hipStream_t stream) const;
+    // labels [n] = lo_build pairs (device) -> ids in place, recons [n][d] (device)
+    void reconstruct_pairs_device(idx_t n, idx_t* labels, float* recons, hipStream_t stream) const;
+
     virtual void train_encoder(idx_t n, const float* x, const idx_t* assign) {}
     // encode n vectors assigned to lists (host in/out); codes [n][code_size]
     virtual void encode_vectors(idx_t n, const float* x, const idx_t* list_nos,
@@ -625,6 +710,9 @@ struct IndexIVF : Index {
                     idx_t* rows) const;
 
    protected:
+    // a change of the host lists: the next search uploads the arena again and
+    // captured search graphs retire (content_version() moves)
+    void mark_mutated();
     virtual void upload_extra() const {}
     // the filter's stream image (debug_rows what = 2): pointer and row bytes,
     // nullptr when this index has none
@@ -740,6 +828,12 @@ struct IndexIVF : Index {
                               const float* cdis, int np, float radius, const uint8_t* sel,
                               uint32_t* counts, const uint64_t* offs, float* D, idx_t* I,
                               bool store_pairs, hipStream_t s) const;
+    // the index-type part of kern::ReconsArgs
+    virtual void recons_args(void* args) const = 0;
+
+   public:
+    // decode the entry at (list_no, offset) of the host lists
+    virtual void reconstruct_from_offset(int64_t list_no, int64_t offset, float* recons) const = 0;
 
    private:
     idx_t search_chunk(idx_t n, size_t np, idx_t k) const;
@@ -761,11 +855,14 @@ struct IndexIVFFlat : IndexIVF {
                                    float* distances, idx_t* labels, hipStream_t stream,
                                    const uint32_t* lim = nullptr, const uint8_t* sel = nullptr,
                                    bool store_pairs = false) const override;
+    // with a direct map: through it; without one: a walk over the lists
     void reconstruct(idx_t key, float* recons) const override;
+    void reconstruct_from_offset(int64_t list_no, int64_t offset, float* recons) const override;
 
    protected:
     void upload_extra() const override;
     void exact_args(void* args) const override;
+    void recons_args(void* args) const override;
     const void* stream_image(size_t* row_bytes) const override;
     // one pass of the range scan (counts when offs == nullptr, else fill);
     // cdis = coarse distances [n][np] on the device (PQ table 1 dis0)
@@ -785,6 +882,8 @@ struct ProductQuantizer {
     ProductQuantizer() = default;
     ProductQuantizer(size_t d, size_t M, size_t nbits);
     void set_derived_values();
+    // faiss/impl/ProductQuantizer.cpp:343-375: one packed code -> d floats
+    void decode(const uint8_t* code, float* x) const;
 };
 
 struct IndexIVFPQ : IndexIVF {
@@ -804,8 +903,11 @@ struct IndexIVFPQ : IndexIVF {
     // faiss/IndexIVFPQ.cpp:364-459: choose 0/1 like the reference (the GPU
     // path uses per-code terms either way)
     void precompute_table();
+    // faiss/IndexIVFPQ.cpp:314-329
+    void reconstruct_from_offset(int64_t list_no, int64_t offset, float* recons) const override;
 
    protected:
+    void recons_args(void* args) const override;
     void own_coarse_dis(idx_t n, const float* x, int ldx, int np, const int32_t* assign,
                         float* cdis, hipStream_t s) const override;
     void upload_extra() const override;
@@ -886,6 +988,8 @@ struct IndexIVFScalarQuantizer : IndexIVF {
     // faiss/IndexScalarQuantizer.cpp:207-260: add to the lists precomputed_idx
     // names (nullptr: the quantizer assigns; < 0: not stored)
     void add_core(idx_t n, const float* x, const idx_t* xids, const idx_t* precomputed_idx);
+    // faiss/IndexScalarQuantizer.cpp:262-279
+    void reconstruct_from_offset(int64_t list_no, int64_t offset, float* recons) const override;
     // not offered on this index type: throws, naming it
     void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result,
                       const SearchParameters* params = nullptr) const override;
@@ -893,6 +997,7 @@ struct IndexIVFScalarQuantizer : IndexIVF {
    protected:
     void upload_extra() const override;
     void exact_args(void* args) const override;
+    void recons_args(void* args) const override;
     void range_launch(const float* x, idx_t n, int ldx, const int32_t* assign, const float* cdis,
                       int np, float radius, const uint8_t* sel, uint32_t* counts,
                       const uint64_t* offs, float* D, idx_t* I, bool store_pairs,

@@ -108,7 +108,9 @@ int faiss_Index_reset(FaissIndex* index);
 /* Index_c.h:121-126: labels [n][k] of the k nearest (the search without the
  * distances) */
 int faiss_Index_assign(FaissIndex* index, idx_t n, const float* x, idx_t* labels, idx_t k);
-/* Index_c.h:196-205 (IndexFlat / IndexIVFFlat / IndexHNSWFlat storage) */
+/* Index_c.h:196-205 (IndexFlat, IndexHNSWFlat storage, IndexRefine; the IVF
+ * classes through their direct map — IndexIVFFlat without one walks its
+ * lists — and reconstruct_n of an IVF index in one pass over the lists) */
 int faiss_Index_reconstruct(const FaissIndex* index, idx_t key, float* recons);
 int faiss_Index_reconstruct_n(const FaissIndex* index, idx_t i0, idx_t ni, float* recons);
 
@@ -150,6 +152,10 @@ int faiss_IDSelectorRange_new(FaissIDSelectorRange** p_sel, idx_t imin, idx_t im
 int faiss_IDSelectorBatch_new(FaissIDSelectorBatch** p_sel, size_t n, const idx_t* indices);
 /* extension: faiss::IDSelectorArray (faiss/impl/IDSelector.h:54-66), ids borrowed */
 int faiss_amd_IDSelectorArray_new(FaissIDSelector** p_sel, size_t n, const idx_t* ids);
+int faiss_IDSelectorArray_new(FaissIDSelector** p_sel, size_t n, const idx_t* ids);
+/* Index_c.h:174-181: IndexFlat and the IndexIVF classes; other types return
+ * -2 ("remove_ids not implemented for this type of index") */
+int faiss_Index_remove_ids(FaissIndex* index, const FaissIDSelector* sel, size_t* n_removed);
 int faiss_IDSelectorBitmap_new(FaissIDSelectorBitmap** p_sel, size_t n, const uint8_t* bitmap);
 int faiss_IDSelectorNot_new(FaissIDSelectorNot** p_sel, const FaissIDSelector* sel);
 int faiss_IDSelectorAnd_new(FaissIDSelectorAnd** p_sel, const FaissIDSelector* lhs_sel,
@@ -274,6 +280,41 @@ int faiss_IndexIVF_search_preassigned(
         int store_pairs);
 /* IndexIVF_c.h:123 */
 size_t faiss_IndexIVF_get_list_size(const FaissIndexIVF* index, size_t list_no);
+/* IndexIVF_c.h:125-132: an Array direct map (ids 0 .. ntotal - 1), or none */
+int faiss_IndexIVF_make_direct_map(FaissIndexIVF* index, int new_maintain_direct_map);
+/* extensions (faiss/IndexIVF.h, faiss/invlists/DirectMap.h; not in the
+ * reference's C API).  Direct map types: 0 NoMap, 1 Array, 2 Hashtable. */
+int faiss_amd_IndexIVF_set_direct_map_type(FaissIndexIVF* index, int type);
+/* the type, or -1 (faiss_get_last_error) when index is not an IndexIVF */
+int faiss_amd_IndexIVF_direct_map_type(const FaissIndexIVF* index);
+/* *lo = (list << 32) | offset of id; the reference's messages when it has none */
+int faiss_amd_IndexIVF_direct_map_get(const FaissIndexIVF* index, idx_t id, idx_t* lo);
+/* IndexIVF::update_vectors on any IVF class (needs a direct map) */
+int faiss_amd_IndexIVF_update_vectors(
+        FaissIndexIVF* index,
+        int nv,
+        const idx_t* idx,
+        const float* v);
+/* ArrayInvertedLists::materialize(): lists mapped from a file (IO_FLAG_MMAP,
+ * `ilod`) are copied to host memory; remove_ids / update_vectors and adds
+ * under a direct map refuse mapped lists */
+int faiss_amd_IndexIVF_materialize_invlists(FaissIndexIVF* index);
+int faiss_amd_IndexIVF_reconstruct_from_offset(
+        const FaissIndexIVF* index,
+        int64_t list_no,
+        int64_t offset,
+        float* recons);
+/* IndexIVF::search_and_reconstruct: recons [n][k][d]; a slot without a result
+ * has label -1 and d words of 0xFFFFFFFF.  params may be NULL. */
+int faiss_amd_IndexIVF_search_and_reconstruct(
+        const FaissIndexIVF* index,
+        idx_t n,
+        const float* x,
+        idx_t k,
+        const FaissSearchParameters* params,
+        float* distances,
+        idx_t* labels,
+        float* recons);
 /* IndexIVF_c.h:46-52, 141: destructor, downcast, list-size imbalance
  * (faiss/invlists/InvertedLists.cpp imbalance_factor: nlist * sum(size^2) /
  * sum(size)^2) */
@@ -371,6 +412,8 @@ void faiss_IndexIVFFlat_set_nprobe(FaissIndexIVFFlat*, size_t);
 FaissIndex* faiss_IndexIVFFlat_quantizer(const FaissIndexIVFFlat*);
 int faiss_IndexIVFFlat_own_fields(const FaissIndexIVFFlat*);
 void faiss_IndexIVFFlat_set_own_fields(FaissIndexIVFFlat*, int);
+/* IndexIVFFlat_c.h:67-79 */
+int faiss_IndexIVFFlat_update_vectors(FaissIndexIVFFlat* index, int nv, idx_t* idx, const float* v);
 
 /* ---------------- IndexIVFPQ (no reference C binding; mirrors the C++
  * constructor faiss/IndexIVFPQ.h:IndexIVFPQ(quantizer,d,nlist,M,nbits)) --- */
@@ -398,6 +441,9 @@ int faiss_amd_IndexIVFPQ_info(
  * table the reference's scanner would use (0 or 1); selects the exact
  * arithmetic of the GPU re-rank.  0 is always valid, 1 needs by_residual L2 */
 int faiss_amd_IndexIVFPQ_set_use_precomputed_table(FaissIndexIVFPQ* index, int v);
+/* IndexIVFPQ::by_residual, on an empty index (the codes added afterwards
+ * encode the vectors themselves when 0) */
+int faiss_amd_IndexIVFPQ_set_by_residual(FaissIndexIVFPQ* index, int v);
 
 /* ---------------- IndexIVFScalarQuantizer (c_api/IndexScalarQuantizer_c.h) -
  * The IVF declarations of that header (:51 to its end).  QT_8bit and QT_fp16
@@ -696,6 +742,29 @@ int faiss_amd_IndexIVF_search_preassigned_device(
         const float* centroid_dis_dev,
         float* distances_dev,
         idx_t* labels_dev,
+        void* stream);
+/* the gather-and-decode kernel of search_and_reconstruct on its own:
+ * labels_dev [n] hold (list << 32) | offset pairs, or a negative value; each
+ * pair becomes the stored id and recons_dev [n][d] the decoded row; a
+ * negative label (or a pair that names no stored row) gives -1 and d words of
+ * 0xFFFFFFFF */
+int faiss_amd_IndexIVF_reconstruct_pairs_device(
+        const FaissIndexIVF* index,
+        idx_t n,
+        idx_t* labels_dev,
+        float* recons_dev,
+        void* stream);
+/* search_and_reconstruct on device pointers (x rows of d floats, d % 4 == 0);
+ * recons_dev [n][k][d] stays in HBM */
+int faiss_amd_IndexIVF_search_and_reconstruct_device(
+        const FaissIndexIVF* index,
+        idx_t n,
+        const float* x_dev,
+        idx_t k,
+        const FaissSearchParameters* params,
+        float* distances_dev,
+        idx_t* labels_dev,
+        float* recons_dev,
         void* stream);
 /* coarse quantization only (device): top-nprobe lists per query */
 int faiss_amd_IndexIVF_quantize_device(
