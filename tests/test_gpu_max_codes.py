@@ -88,11 +88,8 @@ def test_pq_max_codes_matches_oracle(amd, orc, pq_ivf):
         ref = orc.IVFOracle.from_index(pq_ivf)
         Dr, Ir, ndr = ref.search_preassigned(xq, 10, Iq, Dq, max_codes=max_codes,
                                              return_ndis=True)
+        assert_same_results(D, I, Dr, Ir)
         assert ndis == ndr
-        # PQ parity: the LUT summation order differs
-        assert np.mean(I == Ir) > 0.99
-        ok = Ir >= 0
-        np.testing.assert_allclose(D[ok], Dr[ok], rtol=1e-4, atol=1e-5)
 
 
 def test_max_codes_through_parameter_space(amd, orc, flat_ivf):
