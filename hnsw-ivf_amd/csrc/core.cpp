@@ -311,7 +311,15 @@ bool IndexFlat::knn_impl(idx_t n, const float* x, int ldx, int k, float* distanc
                          OutIdx* labels, hipStream_t s, void* qimg_out, bool direct) const {
     const int l = ld();
     const int metric_l2 = metric_type == METRIC_L2;
-    if (k > kern::kMaxK) {
+    // Inner product over more than one 2^20-row chunk: the per-chunk select
+    // and (dis, chunk) merge below keep the lexicographic choice on a boundary
+    // tie, and select_fix_ip only sees one chunk's row, so these go to the
+    // whole-row path, whose select carries the heap's arrival-order rule for
+    // any row count.  (L2: lexicographic order is arrival order.)
+    const bool ip_chunked = !metric_l2 && ntotal > ((idx_t)1 << 20);
+    FAISS_THROW_IF_NOT_MSG(!(ip_chunked && k <= kern::kMaxK && sizeof(OutIdx) == 4),
+                           "coarse quantizer larger than 2^20 centroids");
+    if (k > kern::kMaxK || ip_chunked) {
         // large k (e.g. nprobe > 64): whole distance rows in the reference's
         // form (direct below 20 queries, else BLAS form on the fp32 tile) and
         // the exact select with the heap's arrival-order tie rule

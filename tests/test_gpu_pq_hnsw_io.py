@@ -155,6 +155,17 @@ def test_merge_knn_results_device_and_host(amd, orc, gpu):
     Dr, Ir = orc.merge_knn_results(Dall, Iall)
     D, I = amd.merge_knn_results(Dall, Iall)
     assert np.array_equal(I, Ir) and np.array_equal(D, Dr)
+    # the device merge (k_merge_shards) on the same tables
+    import torch
+    dev = torch.device("cuda:0")
+    Dd, Id = torch.from_numpy(Dall).to(dev), torch.from_numpy(Iall).to(dev)
+    Do = torch.empty((n, k), dtype=torch.float32, device=dev)
+    Io = torch.empty((n, k), dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)
+    amd.merge_knn_results_device(n, k, ns, Dd.data_ptr(), Id.data_ptr(), Do.data_ptr(),
+                                 Io.data_ptr())
+    torch.cuda.synchronize(dev)
+    assert np.array_equal(Io.cpu().numpy(), Ir) and np.array_equal(Do.cpu().numpy(), Dr)
 
 
 @pytest.mark.parametrize("table", [1, 0])
