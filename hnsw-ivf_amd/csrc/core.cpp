@@ -194,9 +194,7 @@ void Index::search(idx_t n, const float* x, idx_t k, float* distances, idx_t* la
     h_x_.reserve(sizeof(float) * n * ldx);
     h_d_.reserve(sizeof(float) * n * k);
     h_i_.reserve(sizeof(idx_t) * n * k);
-    if (ldx != d) HIP_CHECK(hipMemsetAsync(h_x_.ptr, 0, sizeof(float) * n * ldx, s));
-    HIP_CHECK(hipMemcpy2DAsync(h_x_.ptr, sizeof(float) * ldx, x, sizeof(float) * d,
-                               sizeof(float) * d, n, hipMemcpyHostToDevice, s));
+    upload_rows(h_x_.as<float>(), ldx, x, (int)d, n, s);
     search_device(n, h_x_.as<float>(), ldx, k, h_d_.as<float>(), h_i_.as<idx_t>(), params, s);
     HIP_CHECK(hipMemcpyAsync(distances, h_d_.ptr, sizeof(float) * n * k, hipMemcpyDeviceToHost,
                              s));
@@ -251,9 +249,7 @@ void IndexFlat::sync_device() const {
     d_xb_.reserve(sizeof(float) * std::max<idx_t>(ntotal, 1) * l);
     d_norms_.reserve(sizeof(float) * std::max<idx_t>(ntotal, 1));
     if (ntotal > 0) {
-        if (l != d) HIP_CHECK(hipMemsetAsync(d_xb_.ptr, 0, sizeof(float) * ntotal * l, s));
-        HIP_CHECK(hipMemcpy2DAsync(d_xb_.ptr, sizeof(float) * l, xb.data(), sizeof(float) * d,
-                                   sizeof(float) * d, ntotal, hipMemcpyHostToDevice, s));
+        upload_rows(d_xb_.as<float>(), l, xb.data(), (int)d, ntotal, s);
         kern::row_norms(d_xb_.as<float>(), ntotal, d, l, d_norms_.as<float>(), s);
         // bf16 hi/lo image + largest norm for the bf16x3 coarse filter
         if (kern::bf3_db_host(d) <= 128) {
@@ -579,9 +575,7 @@ void IndexFlat::range_search(idx_t n, const float* x, float radius, RangeSearchR
     order_.enter(s);
     try {
         bx.reserve(sizeof(float) * n * l);
-        if (l != d) HIP_CHECK(hipMemsetAsync(bx.ptr, 0, sizeof(float) * n * l, s));
-        HIP_CHECK(hipMemcpy2DAsync(bx.ptr, sizeof(float) * l, x, sizeof(float) * d,
-                                   sizeof(float) * d, n, hipMemcpyHostToDevice, s));
+        upload_rows(bx.as<float>(), l, x, (int)d, n, s);
         const uint8_t* mask = nullptr;
         if (sel) {
             const idx_t* ids = device_row_ids(s);
@@ -708,9 +702,7 @@ void kmeans_train(int d, idx_t n, const float* x, int k, int niter, int64_t seed
     bx.reserve(sizeof(float) * nt * ld);
     bd.reserve(sizeof(float) * nt);
     bi.reserve(sizeof(int32_t) * nt);
-    if (ld != d) HIP_CHECK(hipMemsetAsync(bx.ptr, 0, sizeof(float) * nt * ld, s));
-    HIP_CHECK(hipMemcpy2DAsync(bx.ptr, sizeof(float) * ld, xt, sizeof(float) * d,
-                               sizeof(float) * d, nt, hipMemcpyHostToDevice, s));
+    upload_rows(bx.as<float>(), ld, xt, d, nt, s);
     std::vector<int32_t> assign(nt);
     std::vector<float> dis(nt);
     std::vector<double> sums((size_t)k * d);

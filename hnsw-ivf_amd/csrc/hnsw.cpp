@@ -715,9 +715,7 @@ void IndexHNSW::search_stats(idx_t n, const float* x, idx_t k, float* distances,
     bx.reserve(sizeof(float) * n * ldx);
     bd.reserve(sizeof(float) * n * k);
     bi.reserve(sizeof(idx_t) * n * k);
-    if (ldx != d) HIP_CHECK(hipMemsetAsync(bx.ptr, 0, sizeof(float) * n * ldx, s));
-    HIP_CHECK(hipMemcpy2DAsync(bx.ptr, sizeof(float) * ldx, x, sizeof(float) * d,
-                               sizeof(float) * d, n, hipMemcpyHostToDevice, s));
+    upload_rows(bx.as<float>(), ldx, x, (int)d, n, s);
     hipEvent_t e0, e1;
     HIP_CHECK(hipEventCreate(&e0));
     HIP_CHECK(hipEventCreate(&e1));

@@ -961,9 +961,7 @@ void IndexIVF::search_preassigned_stats(idx_t n, const float* x, idx_t k, const 
     bc.reserve(sizeof(float) * n * np);
     bd.reserve(sizeof(float) * n * k);
     bi.reserve(sizeof(idx_t) * n * k);
-    if (ldx != d) HIP_CHECK(hipMemsetAsync(bx.ptr, 0, sizeof(float) * n * ldx, s));
-    HIP_CHECK(hipMemcpy2DAsync(bx.ptr, sizeof(float) * ldx, x, sizeof(float) * d,
-                               sizeof(float) * d, n, hipMemcpyHostToDevice, s));
+    upload_rows(bx.as<float>(), ldx, x, (int)d, n, s);
     HIP_CHECK(hipMemcpyAsync(ba.ptr, a32.data(), sizeof(int32_t) * n * np,
                              hipMemcpyHostToDevice, s));
     if (centroid_dis)
@@ -1117,9 +1115,7 @@ bool IndexIVF::search_host_paged(idx_t n, const float* x, idx_t k, float* distan
     auto h2d = [&](int i) {
         const idx_t r = b[i + 1] - b[i];
         float* dst = bx.as<float>() + b[i] * ldx;
-        if (ldx != d) HIP_CHECK(hipMemsetAsync(dst, 0, sizeof(float) * r * ldx, cs));
-        HIP_CHECK(hipMemcpy2DAsync(dst, sizeof(float) * ldx, x + b[i] * d, sizeof(float) * d,
-                                   sizeof(float) * d, r, hipMemcpyHostToDevice, cs));
+        upload_rows(dst, ldx, x + b[i] * d, (int)d, r, cs);
         if (cs != s) HIP_CHECK(hipEventRecord(host_ev_[i], cs));
     };
     auto d2h = [&](int i) {
@@ -1222,9 +1218,7 @@ void IndexIVF::search_host(idx_t n, const float* x, idx_t k, float* distances, i
     bx.reserve(sizeof(float) * n * ldx);
     bd.reserve(sizeof(float) * n * k);
     bi.reserve(sizeof(idx_t) * n * k);
-    if (ldx != d) HIP_CHECK(hipMemsetAsync(bx.ptr, 0, sizeof(float) * n * ldx, s));
-    HIP_CHECK(hipMemcpy2DAsync(bx.ptr, sizeof(float) * ldx, x, sizeof(float) * d,
-                               sizeof(float) * d, n, hipMemcpyHostToDevice, s));
+    upload_rows(bx.as<float>(), ldx, x, (int)d, n, s);
     const idx_t qchunk = search_chunk(n, np, k);
     std::lock_guard<std::recursive_mutex> g(mu_);
     s_cd_.reserve(sizeof(float) * qchunk * np);
@@ -1626,9 +1620,7 @@ void IndexIVFPQ::encode_vectors(idx_t n, const float* x, const idx_t* list_nos,
     bc.reserve(sizeof(float) * cent.size());
     bp.reserve(sizeof(float) * pq.centroids.size());
     bo.reserve((size_t)n * cs);
-    if (ldx != d) HIP_CHECK(hipMemsetAsync(bx.ptr, 0, sizeof(float) * n * ldx, s));
-    HIP_CHECK(hipMemcpy2DAsync(bx.ptr, sizeof(float) * ldx, x, sizeof(float) * d,
-                               sizeof(float) * d, n, hipMemcpyHostToDevice, s));
+    upload_rows(bx.as<float>(), ldx, x, (int)d, n, s);
     HIP_CHECK(hipMemcpyAsync(ba.ptr, a32.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(bc.ptr, cent.data(), sizeof(float) * cent.size(),
                              hipMemcpyHostToDevice, s));
@@ -2303,9 +2295,7 @@ void IndexIVF::range_search(idx_t n, const float* x, float radius, RangeSearchRe
     bx.reserve(sizeof(float) * n * ldx);
     bcd.reserve(sizeof(float) * n * np);
     bci.reserve(sizeof(int32_t) * n * np);
-    if (ldx != d) HIP_CHECK(hipMemsetAsync(bx.ptr, 0, sizeof(float) * n * ldx, s));
-    HIP_CHECK(hipMemcpy2DAsync(bx.ptr, sizeof(float) * ldx, x, sizeof(float) * d,
-                               sizeof(float) * d, n, hipMemcpyHostToDevice, s));
+    upload_rows(bx.as<float>(), ldx, x, (int)d, n, s);
     const auto t0 = std::chrono::steady_clock::now();
     quantize_device(n, bx.as<float>(), ldx, (int)np, bcd.as<float>(), bci.as<int32_t>(),
                     params ? params->quantizer_params : nullptr, s);
@@ -2355,9 +2345,7 @@ void IndexIVF::range_search_preassigned(idx_t n, const float* x, float radius,
         HIP_CHECK(hipMemcpyAsync(bcd.ptr, centroid_dis, sizeof(float) * n * np,
                                  hipMemcpyHostToDevice, s));
     }
-    if (ldx != d) HIP_CHECK(hipMemsetAsync(bx.ptr, 0, sizeof(float) * n * ldx, s));
-    HIP_CHECK(hipMemcpy2DAsync(bx.ptr, sizeof(float) * ldx, x, sizeof(float) * d,
-                               sizeof(float) * d, n, hipMemcpyHostToDevice, s));
+    upload_rows(bx.as<float>(), ldx, x, (int)d, n, s);
     HIP_CHECK(hipMemcpyAsync(bci.ptr, a32.data(), sizeof(int32_t) * a32.size(),
                              hipMemcpyHostToDevice, s));
     const uint8_t* selm = apply_selector(params, s);

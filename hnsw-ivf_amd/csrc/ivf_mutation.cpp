@@ -437,9 +437,7 @@ void IndexIVF::search_and_reconstruct(idx_t n, const float* x, idx_t k, float* d
     bd.reserve(sizeof(float) * n * k);
     bi.reserve(sizeof(idx_t) * n * k);
     br.reserve(sizeof(float) * n * k * d);
-    if (ldx != d) HIP_CHECK(hipMemsetAsync(bx.ptr, 0, sizeof(float) * n * ldx, s));
-    HIP_CHECK(hipMemcpy2DAsync(bx.ptr, sizeof(float) * ldx, x, sizeof(float) * d,
-                               sizeof(float) * d, n, hipMemcpyHostToDevice, s));
+    upload_rows(bx.as<float>(), ldx, x, (int)d, n, s);
     search_and_reconstruct_device(n, bx.as<float>(), ldx, k, bd.as<float>(), bi.as<idx_t>(),
                                   br.as<float>(), params, s);
     HIP_CHECK(hipMemcpyAsync(distances, bd.ptr, sizeof(float) * n * k, hipMemcpyDeviceToHost, s));

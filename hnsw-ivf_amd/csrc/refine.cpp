@@ -173,9 +173,7 @@ void IndexRefine::range_search(idx_t n, const float* x, float radius, RangeSearc
     bl.reserve(sizeof(size_t) * (n + 1));
     bi.reserve(sizeof(idx_t) * tot);
     bd.reserve(sizeof(float) * tot);
-    if (ldx != d) HIP_CHECK(hipMemsetAsync(bx.ptr, 0, sizeof(float) * n * ldx, s));
-    HIP_CHECK(hipMemcpy2DAsync(bx.ptr, sizeof(float) * ldx, x, sizeof(float) * d,
-                               sizeof(float) * d, n, hipMemcpyHostToDevice, s));
+    upload_rows(bx.as<float>(), ldx, x, (int)d, n, s);
     HIP_CHECK(hipMemcpyAsync(bl.ptr, result->lims.data(), sizeof(size_t) * (n + 1),
                              hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(bi.ptr, result->labels.data(), sizeof(idx_t) * tot,
