@@ -280,6 +280,37 @@ def _declare(L):
         "faiss_amd_IndexRefine_refine_index": (_P, [_P]),
         "faiss_amd_IndexRefineSearchParameters_new": (C.c_int, [C.c_float, _P, C.POINTER(_P)]),
         "faiss_amd_IndexRefineSearchParameters_free": (None, [_P]),
+        "faiss_VectorTransform_free": (None, [_P]),
+        "faiss_VectorTransform_is_trained": (C.c_int, [_P]),
+        "faiss_VectorTransform_d_in": (C.c_int, [_P]),
+        "faiss_VectorTransform_d_out": (C.c_int, [_P]),
+        "faiss_VectorTransform_train": (C.c_int, [_P, _I64, _P]),
+        "faiss_amd_VectorTransform_apply_noalloc": (C.c_int, [_P, _I64, _P, _P]),
+        "faiss_amd_VectorTransform_reverse_transform": (C.c_int, [_P, _I64, _P, _P]),
+        "faiss_amd_VectorTransform_type": (C.c_char_p, [_P]),
+        "faiss_LinearTransform_have_bias": (C.c_int, [_P]),
+        "faiss_LinearTransform_is_orthonormal": (C.c_int, [_P]),
+        "faiss_amd_LinearTransform_new": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int]),
+        "faiss_amd_LinearTransform_set": (C.c_int, [_P, _P, _P]),
+        "faiss_amd_LinearTransform_A": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float)),
+                                                  C.POINTER(C.c_size_t)]),
+        "faiss_amd_LinearTransform_b": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float)),
+                                                  C.POINTER(C.c_size_t)]),
+        "faiss_amd_linear_transform_device": (C.c_int, [_P, _I64, C.c_int, _P, C.c_int, C.c_int,
+                                                        _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+        "faiss_IndexPreTransform_new_with": (C.c_int, [C.POINTER(_P), _P]),
+        "faiss_IndexPreTransform_new_with_transform": (C.c_int, [C.POINTER(_P), _P, _P]),
+        "faiss_IndexPreTransform_prepend_transform": (C.c_int, [_P, _P]),
+        "faiss_IndexPreTransform_index": (_P, [_P]),
+        "faiss_IndexPreTransform_own_fields": (C.c_int, [_P]),
+        "faiss_amd_IndexPreTransform_chain_size": (C.c_int, [_P]),
+        "faiss_amd_IndexPreTransform_chain_at": (_P, [_P, C.c_int]),
+        "faiss_amd_IndexPreTransform_apply_chain": (C.c_int, [_P, _I64, _P, _P]),
+        "faiss_amd_IndexPreTransform_reverse_chain": (C.c_int, [_P, _I64, _P, _P]),
+        "faiss_amd_IndexPreTransform_search_and_reconstruct": (C.c_int, [_P, _I64, _P, _I64, _P,
+                                                                         _P, _P, _P]),
+        "faiss_amd_SearchParametersPreTransform_new": (C.c_int, [_P, C.POINTER(_P)]),
+        "faiss_amd_SearchParametersPreTransform_free": (None, [_P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -930,6 +961,207 @@ class IndexRefineFlat(Index):
         return _wrap(lib().faiss_amd_IndexRefine_refine_index(self.h), owner=self)
 
 
+class VectorTransform:
+    """A faiss.VectorTransform handle (owned unless `owner` is set): applied on
+    the GPU; a vector transforms to the same bits in any batch."""
+
+    def __init__(self, handle, owner=None):
+        self.h = C.c_void_p(handle) if not isinstance(handle, C.c_void_p) else handle
+        self._owner = owner
+
+    def __del__(self):
+        try:
+            if self._owner is None and self.h and self.h.value and _lib is not None:
+                _lib.faiss_VectorTransform_free(self.h)
+                self.h = C.c_void_p(None)
+        except Exception:
+            pass
+
+    @property
+    def d_in(self):
+        return lib().faiss_VectorTransform_d_in(self.h)
+
+    @property
+    def d_out(self):
+        return lib().faiss_VectorTransform_d_out(self.h)
+
+    @property
+    def is_trained(self):
+        return bool(lib().faiss_VectorTransform_is_trained(self.h))
+
+    @property
+    def type_name(self):
+        return lib().faiss_amd_VectorTransform_type(self.h).decode()
+
+    def train(self, x):
+        x = _f32(x)
+        _check(lib().faiss_VectorTransform_train(self.h, x.shape[0], _ptr(x)))
+
+    def apply(self, x):
+        x = _f32(x)
+        xt = np.empty((x.shape[0], self.d_out), dtype=np.float32)
+        _check(lib().faiss_amd_VectorTransform_apply_noalloc(self.h, x.shape[0], _ptr(x),
+                                                             _ptr(xt)))
+        return xt
+
+    def reverse_transform(self, xt):
+        xt = _f32(xt)
+        x = np.empty((xt.shape[0], self.d_in), dtype=np.float32)
+        _check(lib().faiss_amd_VectorTransform_reverse_transform(self.h, xt.shape[0], _ptr(xt),
+                                                                 _ptr(x)))
+        return x
+
+
+class LinearTransform(VectorTransform):
+    """faiss.LinearTransform: xt = A x + b with A [d_out][d_in].  Given A (and
+    b) it is trained; is_orthonormal follows the reference's test."""
+
+    def __init__(self, d_in=None, d_out=None, have_bias=False, A=None, b=None, handle=None,
+                 owner=None):
+        if handle is None:
+            if A is not None:
+                A = np.ascontiguousarray(A, dtype=np.float32)
+                d_out, d_in = A.shape
+            p = C.c_void_p()
+            _check(lib().faiss_amd_LinearTransform_new(C.byref(p), d_in, d_out,
+                                                       int(bool(have_bias) or b is not None)))
+            handle = p
+        super().__init__(handle, owner)
+        if A is not None:
+            self.set(A, b)
+
+    def set(self, A, b=None):
+        A = np.ascontiguousarray(A, dtype=np.float32)
+        assert A.shape == (self.d_out, self.d_in)
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.float32)
+            assert b.shape == (self.d_out,)
+        _check(lib().faiss_amd_LinearTransform_set(self.h, _ptr(A),
+                                                   _ptr(b) if b is not None else None))
+
+    def _vec(self, fn):
+        p, n = C.POINTER(C.c_float)(), C.c_size_t(0)
+        _check(fn(self.h, C.byref(p), C.byref(n)))
+        return (np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value
+                else np.zeros(0, np.float32))
+
+    @property
+    def A(self):
+        return self._vec(lib().faiss_amd_LinearTransform_A)
+
+    @property
+    def b(self):
+        return self._vec(lib().faiss_amd_LinearTransform_b)
+
+    @property
+    def have_bias(self):
+        return bool(lib().faiss_LinearTransform_have_bias(self.h))
+
+    @property
+    def is_orthonormal(self):
+        return bool(lib().faiss_LinearTransform_is_orthonormal(self.h))
+
+
+class IndexPreTransform(Index):
+    """faiss.IndexPreTransform: vectors go through a chain of transforms on
+    the GPU into the sub-index.  IndexPreTransform(index) or
+    IndexPreTransform(ltrans, index); neither argument is owned."""
+
+    def __init__(self, *args, handle=None, owner=None):
+        if handle is None:
+            p = C.c_void_p()
+            if len(args) == 1:
+                _check(lib().faiss_IndexPreTransform_new_with(C.byref(p), args[0].h))
+            else:
+                _check(lib().faiss_IndexPreTransform_new_with_transform(C.byref(p), args[0].h,
+                                                                        args[1].h))
+            handle = p
+            self._parts = list(args)  # must outlive the wrapper (own_fields = false)
+        super().__init__(handle, owner)
+
+    def prepend_transform(self, ltrans):
+        _check(lib().faiss_IndexPreTransform_prepend_transform(self.h, ltrans.h))
+        if hasattr(self, "_parts"):
+            self._parts.append(ltrans)
+
+    @property
+    def index(self):
+        return _wrap(lib().faiss_IndexPreTransform_index(self.h), owner=self)
+
+    @property
+    def own_fields(self):
+        return bool(lib().faiss_IndexPreTransform_own_fields(self.h))
+
+    @property
+    def chain(self):
+        out = []
+        for i in range(lib().faiss_amd_IndexPreTransform_chain_size(self.h)):
+            h = C.c_void_p(lib().faiss_amd_IndexPreTransform_chain_at(self.h, i))
+            name = lib().faiss_amd_VectorTransform_type(h).decode()
+            cls = VectorTransform if name == "VectorTransform" else LinearTransform
+            out.append(cls(handle=h, owner=self))
+        return out
+
+    def apply_chain(self, x):
+        x = _f32(x)
+        d_sub = lib().faiss_Index_d(lib().faiss_IndexPreTransform_index(self.h))
+        xt = np.empty((x.shape[0], d_sub), dtype=np.float32)
+        _check(lib().faiss_amd_IndexPreTransform_apply_chain(self.h, x.shape[0], _ptr(x),
+                                                             _ptr(xt)))
+        return xt
+
+    def reverse_chain(self, xt):
+        xt = _f32(xt)
+        x = np.empty((xt.shape[0], self.d), dtype=np.float32)
+        _check(lib().faiss_amd_IndexPreTransform_reverse_chain(self.h, xt.shape[0], _ptr(xt),
+                                                               _ptr(x)))
+        return x
+
+    def search_and_reconstruct(self, x, k, params=None):
+        x = _f32(x)
+        n = x.shape[0]
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.int64)
+        R = np.empty((n, k, self.d), dtype=np.float32)
+        _check(lib().faiss_amd_IndexPreTransform_search_and_reconstruct(
+            self.h, n, _ptr(x), k, params.h if params is not None else None, _ptr(D), _ptr(I),
+            _ptr(R)))
+        return D, I, R
+
+
+def apply_chain(index, x):
+    """index.apply_chain(x) for an IndexPreTransform."""
+    return index.apply_chain(x)
+
+
+class SearchParametersPreTransform:
+    """faiss.SearchParametersPreTransform: index_params go to the sub-index."""
+
+    def __init__(self, index_params=None):
+        p = C.c_void_p()
+        _check(lib().faiss_amd_SearchParametersPreTransform_new(
+            index_params.h if index_params else None, C.byref(p)))
+        self.h = p
+        self.index_params = index_params  # must outlive the searches that use it
+
+    def __del__(self):
+        try:
+            lib().faiss_amd_SearchParametersPreTransform_free(self.h)
+        except Exception:
+            pass
+
+
+def linear_transform_device(in_ptr, n, ld_in, A_ptr, d_in, d_out, b_ptr, out_ptr, ld_out,
+                            transposed=False, variant=0, stream=None):
+    """kern::linear_transform on device pointers: out [n][ld_out] = in through
+    A [d_out][d_in] and b (0: none); transposed: out = A^T (in - b).  variant
+    1 / 2 force the 128- / 32-row tile."""
+    _check(lib().faiss_amd_linear_transform_device(
+        C.c_void_p(in_ptr), n, ld_in, C.c_void_p(A_ptr), d_in, d_out, C.c_void_p(b_ptr or 0),
+        C.c_void_p(out_ptr), ld_out, int(bool(transposed)), int(variant),
+        C.c_void_p(stream or 0)))
+
+
 class IndexShardsIVF(IndexIVF):
     """faiss/IndexShardsIVF.h: shards sharing one coarse quantizer; shards on
     other devices than the quantizer are searched over RCCL (shards.cpp)."""
@@ -1144,7 +1376,8 @@ def _wrap(h, owner=None):
     cls = {"IndexIVFPQ": IndexIVFPQ, "IndexIVFFlat": IndexIVFFlat,
            "IndexIVFScalarQuantizer": IndexIVFScalarQuantizer,
            "IndexHNSWFlat": IndexHNSWFlat, "IndexFlat": IndexFlat,
-           "IndexRefineFlat": IndexRefineFlat}.get(t)
+           "IndexRefineFlat": IndexRefineFlat,
+           "IndexPreTransform": IndexPreTransform}.get(t)
     if cls is None:
         return Index(h, owner)
     return cls(handle=h, owner=owner)

@@ -39,14 +39,37 @@ inline Index* IX(FaissIndex* p) { return reinterpret_cast<Index*>(p); }
 inline const Index* IX(const FaissIndex* p) { return reinterpret_cast<const Index*>(p); }
 inline FaissIndex* FX(Index* p) { return reinterpret_cast<FaissIndex*>(p); }
 
+// the sub-index of IndexPreTransform wrappers (faiss/IVFlib.cpp:62-83 looks
+// through them for the IndexIVF)
+const Index* under_pretransform(const Index* ix) {
+    while (auto pt = dynamic_cast<const IndexPreTransform*>(ix)) ix = pt->index;
+    return ix;
+}
 IndexIVF* IVF(FaissIndex* p) {
-    auto r = dynamic_cast<IndexIVF*>(IX(p));
+    auto r = dynamic_cast<IndexIVF*>(const_cast<Index*>(under_pretransform(IX(p))));
     FAISS_THROW_IF_NOT_MSG(r, "index is not an IndexIVF");
     return r;
 }
 const IndexIVF* IVF(const FaissIndex* p) {
-    auto r = dynamic_cast<const IndexIVF*>(IX(p));
+    auto r = dynamic_cast<const IndexIVF*>(under_pretransform(IX(p)));
     FAISS_THROW_IF_NOT_MSG(r, "index is not an IndexIVF");
+    return r;
+}
+struct PreTransformParamsC {
+    SearchParametersPreTransform pt;
+};
+inline VectorTransform* VT(FaissVectorTransform* p) { return reinterpret_cast<VectorTransform*>(p); }
+inline const VectorTransform* VT(const FaissVectorTransform* p) {
+    return reinterpret_cast<const VectorTransform*>(p);
+}
+LinearTransform* LT(const FaissVectorTransform* p) {
+    auto r = dynamic_cast<LinearTransform*>(const_cast<VectorTransform*>(VT(p)));
+    FAISS_THROW_IF_NOT_MSG(r, "transform is not a LinearTransform");
+    return r;
+}
+IndexPreTransform* PT(const FaissIndex* p) {
+    auto r = dynamic_cast<IndexPreTransform*>(const_cast<Index*>(IX(p)));
+    FAISS_THROW_IF_NOT_MSG(r, "index is not an IndexPreTransform");
     return r;
 }
 }  // namespace
@@ -107,6 +130,7 @@ static const SearchParameters* resolve_params(const FaissSearchParameters* p) {
     if (!p) return nullptr;
     auto base = reinterpret_cast<const SearchParameters*>(p);
     if (dynamic_cast<const IndexRefineSearchParameters*>(base)) return base;
+    if (dynamic_cast<const SearchParametersPreTransform*>(base)) return base;
     if (dynamic_cast<const SearchParametersHNSW*>(base)) return base;
     auto sp = reinterpret_cast<const SearchParamsC*>(p);
     return &sp->ivf;
@@ -449,9 +473,267 @@ void faiss_amd_IndexRefineSearchParameters_free(FaissSearchParameters* obj) {
     delete reinterpret_cast<RefineParamsC*>(obj);
 }
 
+// ---------------- VectorTransform (c_api/VectorTransform_c.h)
+// The reference declares apply_noalloc, reverse_transform, transform_transpose
+// and set_is_orthonormal void: a failure leaves its message for
+// faiss_get_last_error() and the output untouched.
+#define C_VOID_TRY try {
+#define C_VOID_CATCH                  \
+    }                                 \
+    catch (std::exception & e) {      \
+        g_last_error = e.what();      \
+    }                                 \
+    catch (...) {                     \
+        g_last_error = "Unknown error"; \
+    }
+void faiss_VectorTransform_free(FaissVectorTransform* obj) { delete VT(obj); }
+int faiss_VectorTransform_is_trained(const FaissVectorTransform* vt) { return VT(vt)->is_trained; }
+int faiss_VectorTransform_d_in(const FaissVectorTransform* vt) { return VT(vt)->d_in; }
+int faiss_VectorTransform_d_out(const FaissVectorTransform* vt) { return VT(vt)->d_out; }
+int faiss_VectorTransform_train(FaissVectorTransform* vt, idx_t n, const float* x) {
+    C_TRY VT(vt)->train(n, x);
+    C_CATCH
+}
+float* faiss_VectorTransform_apply(const FaissVectorTransform* vt, idx_t n, const float* x) {
+    C_VOID_TRY return VT(vt)->apply(n, x);
+    C_VOID_CATCH
+    return nullptr;
+}
+void faiss_VectorTransform_apply_noalloc(const FaissVectorTransform* vt, idx_t n, const float* x,
+                                         float* xt) {
+    C_VOID_TRY VT(vt)->apply_noalloc(n, x, xt);
+    C_VOID_CATCH
+}
+void faiss_VectorTransform_reverse_transform(const FaissVectorTransform* vt, idx_t n,
+                                             const float* xt, float* x) {
+    C_VOID_TRY VT(vt)->reverse_transform(n, xt, x);
+    C_VOID_CATCH
+}
+// the same two with a return code (not in the reference C API)
+int faiss_amd_VectorTransform_apply_noalloc(const FaissVectorTransform* vt, idx_t n,
+                                            const float* x, float* xt) {
+    C_TRY VT(vt)->apply_noalloc(n, x, xt);
+    C_CATCH
+}
+int faiss_amd_VectorTransform_reverse_transform(const FaissVectorTransform* vt, idx_t n,
+                                                const float* xt, float* x) {
+    C_TRY VT(vt)->reverse_transform(n, xt, x);
+    C_CATCH
+}
+const char* faiss_amd_VectorTransform_type(const FaissVectorTransform* vt) {
+    const VectorTransform* t = VT(vt);
+    if (dynamic_cast<const RandomRotationMatrix*>(t)) return "RandomRotationMatrix";
+    if (dynamic_cast<const PCAMatrix*>(t)) return "PCAMatrix";
+    if (dynamic_cast<const OPQMatrix*>(t)) return "OPQMatrix";
+    if (dynamic_cast<const LinearTransform*>(t)) return "LinearTransform";
+    return "VectorTransform";
+}
+void faiss_LinearTransform_free(FaissLinearTransform* obj) { delete VT(obj); }
+void faiss_LinearTransform_transform_transpose(const FaissLinearTransform* vt, idx_t n,
+                                               const float* y, float* x) {
+    C_VOID_TRY LT(vt)->transform_transpose(n, y, x);
+    C_VOID_CATCH
+}
+void faiss_LinearTransform_set_is_orthonormal(FaissLinearTransform* vt) {
+    C_VOID_TRY LT(vt)->set_is_orthonormal();
+    C_VOID_CATCH
+}
+int faiss_LinearTransform_have_bias(const FaissLinearTransform* vt) {
+    auto t = dynamic_cast<const LinearTransform*>(VT(vt));
+    return t ? t->have_bias : 0;
+}
+int faiss_LinearTransform_is_orthonormal(const FaissLinearTransform* vt) {
+    auto t = dynamic_cast<const LinearTransform*>(VT(vt));
+    return t ? t->is_orthonormal : 0;
+}
+int faiss_amd_LinearTransform_new(FaissLinearTransform** p_vt, int d_in, int d_out,
+                                  int have_bias) {
+    C_TRY* p_vt = reinterpret_cast<FaissLinearTransform*>(
+            static_cast<VectorTransform*>(new LinearTransform(d_in, d_out, have_bias != 0)));
+    C_CATCH
+}
+// A [d_out][d_in] and b [d_out] (NULL: no bias) are copied; the transform
+// counts as trained and is_orthonormal is set by the reference's test
+int faiss_amd_LinearTransform_set(FaissLinearTransform* vt, const float* A, const float* b) {
+    C_TRY LinearTransform* t = LT(vt);
+    FAISS_THROW_IF_NOT_MSG(A, "LinearTransform: no matrix");
+    t->A.assign(A, A + (size_t)t->d_in * t->d_out);
+    t->have_bias = b != nullptr;
+    if (b)
+        t->b.assign(b, b + t->d_out);
+    else
+        t->b.clear();
+    t->is_trained = true;
+    t->set_is_orthonormal();
+    C_CATCH
+}
+int faiss_amd_LinearTransform_A(const FaissLinearTransform* vt, const float** A, size_t* n) {
+    C_TRY* A = LT(vt)->A.data();
+    *n = LT(vt)->A.size();
+    C_CATCH
+}
+int faiss_amd_LinearTransform_b(const FaissLinearTransform* vt, const float** b, size_t* n) {
+    C_TRY* b = LT(vt)->b.data();
+    *n = LT(vt)->b.size();
+    C_CATCH
+}
+void faiss_RandomRotationMatrix_free(FaissRandomRotationMatrix* obj) { delete VT(obj); }
+int faiss_RandomRotationMatrix_new_with(FaissRandomRotationMatrix** p_vt, int d_in, int d_out) {
+    C_TRY* p_vt = reinterpret_cast<FaissRandomRotationMatrix*>(
+            static_cast<VectorTransform*>(new RandomRotationMatrix(d_in, d_out)));
+    C_CATCH
+}
+void faiss_PCAMatrix_free(FaissPCAMatrix* obj) { delete VT(obj); }
+int faiss_PCAMatrix_new_with(FaissPCAMatrix** p_vt, int d_in, int d_out, float eigen_power,
+                             int random_rotation) {
+    C_TRY* p_vt = reinterpret_cast<FaissPCAMatrix*>(static_cast<VectorTransform*>(
+            new PCAMatrix(d_in, d_out, eigen_power, random_rotation != 0)));
+    C_CATCH
+}
+float faiss_PCAMatrix_eigen_power(const FaissPCAMatrix* vt) {
+    auto t = dynamic_cast<const PCAMatrix*>(VT(vt));
+    return t ? t->eigen_power : 0.f;
+}
+int faiss_PCAMatrix_random_rotation(const FaissPCAMatrix* vt) {
+    auto t = dynamic_cast<const PCAMatrix*>(VT(vt));
+    return t ? t->random_rotation : 0;
+}
+void faiss_OPQMatrix_free(FaissOPQMatrix* obj) { delete VT(obj); }
+int faiss_OPQMatrix_new_with(FaissOPQMatrix** p_vt, int d, int M, int d2) {
+    C_TRY* p_vt = reinterpret_cast<FaissOPQMatrix*>(
+            static_cast<VectorTransform*>(new OPQMatrix(d, M, d2)));
+    C_CATCH
+}
+#define OPQ_FIELD(NAME, FIELD)                                           \
+    int faiss_OPQMatrix_##NAME(const FaissOPQMatrix* vt) {               \
+        auto t = dynamic_cast<const OPQMatrix*>(VT(vt));                 \
+        return t ? (int)t->FIELD : 0;                                    \
+    }                                                                    \
+    void faiss_OPQMatrix_set_##NAME(FaissOPQMatrix* vt, int v) {         \
+        if (auto t = dynamic_cast<OPQMatrix*>(VT(vt))) t->FIELD = v;     \
+    }
+OPQ_FIELD(verbose, verbose)
+OPQ_FIELD(niter, niter)
+OPQ_FIELD(niter_pq, niter_pq)
+#undef OPQ_FIELD
+// the transform kinds this path does not serve: the constructors fail with
+// the FaissException code, naming the kind
+static int vt_not_served(const char* kind) {
+    g_last_error = std::string("VectorTransform ") + kind +
+                   " is not served on this path (linear transforms only)";
+    return -2;
+}
+int faiss_ITQMatrix_new_with(FaissVectorTransform**, int) { return vt_not_served("ITQMatrix"); }
+int faiss_ITQTransform_new_with(FaissVectorTransform**, int, int, int) {
+    return vt_not_served("ITQTransform");
+}
+int faiss_RemapDimensionsTransform_new_with(FaissVectorTransform**, int, int, int) {
+    return vt_not_served("RemapDimensionsTransform");
+}
+int faiss_NormalizationTransform_new_with(FaissVectorTransform**, int, float) {
+    return vt_not_served("NormalizationTransform");
+}
+int faiss_CenteringTransform_new_with(FaissVectorTransform**, int) {
+    return vt_not_served("CenteringTransform");
+}
+// the kernel alone on device pointers (x [n][ldx], A [d_out][d_in], b [d_out]
+// or NULL, y [n][ldy]); transposed: x = A^T (y - b) with the roles of x and y
+// as in kern::linear_transform_transposed; variant 0 / 1 / 2 = by n / wide / narrow
+int faiss_amd_linear_transform_device(const float* in, idx_t n, int ld_in, const float* A,
+                                      int d_in, int d_out, const float* b, float* out,
+                                      int ld_out, int transposed, int variant, void* stream) {
+    C_TRY ensure_hip();
+    if (transposed)
+        kern::linear_transform_transposed(in, n, ld_in, A, d_in, d_out, b, out, ld_out,
+                                          (hipStream_t)stream, variant);
+    else
+        kern::linear_transform(in, n, ld_in, A, d_in, d_out, b, out, ld_out, (hipStream_t)stream,
+                               variant);
+    C_CATCH
+}
+
+// ---------------- IndexPreTransform (c_api/IndexPreTransform_c.h)
+void faiss_IndexPreTransform_free(FaissIndexPreTransform* obj) { delete IX(obj); }
+FaissIndexPreTransform* faiss_IndexPreTransform_cast(FaissIndex* index) {
+    return dynamic_cast<IndexPreTransform*>(IX(index)) ? index : nullptr;
+}
+FaissIndex* faiss_IndexPreTransform_index(const FaissIndexPreTransform* i) {
+    auto pt = dynamic_cast<const IndexPreTransform*>(IX(i));
+    return pt ? FX(pt->index) : nullptr;
+}
+int faiss_IndexPreTransform_own_fields(const FaissIndexPreTransform* i) {
+    auto pt = dynamic_cast<const IndexPreTransform*>(IX(i));
+    return pt && pt->own_fields;
+}
+void faiss_IndexPreTransform_set_own_fields(FaissIndexPreTransform* i, int v) {
+    if (auto pt = dynamic_cast<IndexPreTransform*>(IX(i))) pt->own_fields = v != 0;
+}
+int faiss_IndexPreTransform_new(FaissIndexPreTransform** p_index) {
+    C_TRY* p_index = FX(new IndexPreTransform());
+    C_CATCH
+}
+int faiss_IndexPreTransform_new_with(FaissIndexPreTransform** p_index, FaissIndex* index) {
+    C_TRY* p_index = FX(new IndexPreTransform(IX(index)));
+    C_CATCH
+}
+int faiss_IndexPreTransform_new_with_transform(FaissIndexPreTransform** p_index,
+                                               FaissVectorTransform* ltrans, FaissIndex* index) {
+    C_TRY* p_index = FX(new IndexPreTransform(VT(ltrans), IX(index)));
+    C_CATCH
+}
+int faiss_IndexPreTransform_prepend_transform(FaissIndexPreTransform* index,
+                                              FaissVectorTransform* ltrans) {
+    C_TRY PT(index)->prepend_transform(VT(ltrans));
+    C_CATCH
+}
+int faiss_amd_IndexPreTransform_chain_size(const FaissIndexPreTransform* i) {
+    auto pt = dynamic_cast<const IndexPreTransform*>(IX(i));
+    return pt ? (int)pt->chain.size() : 0;
+}
+FaissVectorTransform* faiss_amd_IndexPreTransform_chain_at(const FaissIndexPreTransform* i,
+                                                           int t) {
+    auto pt = dynamic_cast<const IndexPreTransform*>(IX(i));
+    if (!pt || t < 0 || t >= (int)pt->chain.size()) return nullptr;
+    return reinterpret_cast<FaissVectorTransform*>(pt->chain[t]);
+}
+// host rows through the chain: xt [n][index->d] / back: x [n][d]
+int faiss_amd_IndexPreTransform_apply_chain(const FaissIndexPreTransform* index, idx_t n,
+                                            const float* x, float* xt) {
+    C_TRY PT(index)->apply_chain_noalloc(n, x, xt);
+    C_CATCH
+}
+int faiss_amd_IndexPreTransform_reverse_chain(const FaissIndexPreTransform* index, idx_t n,
+                                              const float* xt, float* x) {
+    C_TRY PT(index)->reverse_chain(n, xt, x);
+    C_CATCH
+}
+int faiss_amd_IndexPreTransform_search_and_reconstruct(const FaissIndexPreTransform* index,
+                                                       idx_t n, const float* x, idx_t k,
+                                                       const FaissSearchParameters* params,
+                                                       float* distances, idx_t* labels,
+                                                       float* recons) {
+    C_TRY PT(index)->search_and_reconstruct(n, x, k, distances, labels, recons,
+                                            resolve_params(params));
+    C_CATCH
+}
+int faiss_amd_SearchParametersPreTransform_new(FaissSearchParameters* index_params,
+                                               FaissSearchParameters** p_sp) {
+    C_TRY auto sp = new PreTransformParamsC();
+    sp->pt.index_params = const_cast<SearchParameters*>(resolve_params(index_params));
+    *p_sp = reinterpret_cast<FaissSearchParameters*>(sp);
+    C_CATCH
+}
+void faiss_amd_SearchParametersPreTransform_free(FaissSearchParameters* obj) {
+    delete reinterpret_cast<PreTransformParamsC*>(obj);
+}
+
 // ---------------- IndexIVF (getters never throw: 0 / no-op on a wrong type)
-static const IndexIVF* IVFc(const FaissIndexIVF* i) { return dynamic_cast<const IndexIVF*>(IX(i)); }
-static IndexIVF* IVFm(FaissIndexIVF* i) { return dynamic_cast<IndexIVF*>(IX(i)); }
+static const IndexIVF* IVFc(const FaissIndexIVF* i) {
+    return dynamic_cast<const IndexIVF*>(under_pretransform(IX(i)));
+}
+static IndexIVF* IVFm(FaissIndexIVF* i) {
+    return dynamic_cast<IndexIVF*>(const_cast<Index*>(under_pretransform(IX(i))));
+}
 const char* faiss_amd_Index_type(const FaissIndex* i) {
     return index_type_name(IX(i));
 }
@@ -981,13 +1263,21 @@ int faiss_ParameterSpace_set_index_parameter(const FaissParameterSpace*, FaissIn
     Index* ix = IX(index);
     // faiss/AutoTune.cpp:483-491: k_factor_rf is the wrapper's, every other
     // name goes to its base index
-    while (auto rf = dynamic_cast<IndexRefine*>(ix)) {
-        if (n == "k_factor_rf") {
-            rf->k_factor = (float)(int)val;
-            return 0;
+    // (:476-481: an IndexPreTransform hands every name to its sub-index)
+    for (;;) {
+        if (auto pt = dynamic_cast<IndexPreTransform*>(ix)) {
+            FAISS_THROW_IF_NOT(pt->index);
+            ix = pt->index;
+        } else if (auto rf = dynamic_cast<IndexRefine*>(ix)) {
+            if (n == "k_factor_rf") {
+                rf->k_factor = (float)(int)val;
+                return 0;
+            }
+            FAISS_THROW_IF_NOT(rf->base_index);
+            ix = rf->base_index;
+        } else {
+            break;
         }
-        FAISS_THROW_IF_NOT(rf->base_index);
-        ix = rf->base_index;
         index = FX(ix);
     }
     if (n == "nprobe") {

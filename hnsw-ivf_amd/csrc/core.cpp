@@ -166,6 +166,7 @@ void Index::range_search(idx_t, const float*, float, RangeSearchResult*,
 hipStream_t Index::stream() const { return device_context(device).stream; }
 
 const char* index_type_name(const Index* x) {
+    if (dynamic_cast<const IndexPreTransform*>(x)) return "IndexPreTransform";
     if (dynamic_cast<const IndexRefineFlat*>(x)) return "IndexRefineFlat";
     if (dynamic_cast<const IndexRefine*>(x)) return "IndexRefine";
     if (dynamic_cast<const IndexShardsIVF*>(x)) return "IndexShardsIVF";

@@ -22,6 +22,9 @@
 //             neighbors, entry_point:i32, max_level, efConstruction,
 //             efSearch:int, dummy int), storage index         (:300-316,760-778)
 //   IxRF    = header, base index, refine index, k_factor:f32    (:744-752)
+//   IxPT    = header, nt:i32, nt VectorTransform records, sub-index (:725-735)
+//   VectorTransform = rrot | Pcam + PCA fields | LTra, then have_bias:u8,
+//             A, b, d_in:i32, d_out:i32, is_trained:u8          (:92-153)
 //   vectors carry a size_t element-count prefix (faiss/impl/io_macros.h:62-67)
 //   fourcc = little-endian chars (faiss/impl/io.cpp:237-241)
 #include <fcntl.h>
@@ -440,6 +443,79 @@ void read_invlists(ArrayInvertedLists* il, Reader& r, size_t nlist, size_t code_
 
 void write_index_impl(const Index* idx, Writer& w);
 
+// faiss/impl/index_write.cpp:92-153.  An OPQMatrix has no tag of its own: it
+// is written as a plain "LTra" (and read back as a LinearTransform).
+void write_vt(const VectorTransform* vt, Writer& w) {
+    auto lt = dynamic_cast<const LinearTransform*>(vt);
+    FAISS_THROW_IF_NOT_MSG(lt, "cannot serialize this");
+    if (dynamic_cast<const RandomRotationMatrix*>(lt)) {
+        w.one(fourcc("rrot"));
+    } else if (auto pca = dynamic_cast<const PCAMatrix*>(lt)) {
+        w.one(fourcc("Pcam"));
+        w.one(pca->eigen_power);
+        w.one(pca->epsilon);
+        w.one(pca->random_rotation);
+        w.one(pca->balanced_bins);
+        w.vec(pca->mean);
+        w.vec(pca->eigenvalues);
+        w.vec(pca->PCAMat);
+    } else {
+        w.one(fourcc("LTra"));
+    }
+    w.one(lt->have_bias);
+    w.vec(lt->A);
+    w.vec(lt->b);
+    w.one(vt->d_in);
+    w.one(vt->d_out);
+    w.one(vt->is_trained);
+}
+
+// faiss/impl/index_read.cpp:76-159
+VectorTransform* read_vt(Reader& r) {
+    const uint32_t h = r.one<uint32_t>();
+    std::unique_ptr<LinearTransform> lt;
+    if (h == fourcc("rrot")) {
+        lt.reset(new RandomRotationMatrix());
+    } else if (h == fourcc("PCAm") || h == fourcc("PcAm") || h == fourcc("Pcam")) {
+        auto pca = new PCAMatrix();
+        lt.reset(pca);
+        pca->eigen_power = r.one<float>();
+        if (h == fourcc("Pcam")) pca->epsilon = r.one<float>();
+        pca->random_rotation = r.one<bool>();
+        if (h != fourcc("PCAm")) pca->balanced_bins = r.one<int>();
+        r.vec(pca->mean);
+        r.vec(pca->eigenvalues);
+        r.vec(pca->PCAMat);
+    } else if (h == fourcc("LTra")) {
+        lt.reset(new LinearTransform());
+    } else {
+        static const struct {
+            const char *tag, *kind;
+        } others[] = {{"Viqm", "ITQMatrix"},
+                      {"Viqt", "ITQTransform"},
+                      {"RmDT", "RemapDimensionsTransform"},
+                      {"VNrm", "NormalizationTransform"},
+                      {"VCnt", "CenteringTransform"}};
+        for (auto& o : others)
+            FAISS_THROW_IF_NOT_FMT(h != fourcc(o.tag),
+                                   "VectorTransform %s (\"%s\") is not served on this path "
+                                   "(linear transforms only)",
+                                   o.kind, o.tag);
+        FAISS_THROW_MSG("fourcc \"" + fourcc_str(h) + "\" not recognized as a VectorTransform");
+    }
+    lt->have_bias = r.one<bool>();
+    r.vec(lt->A);
+    r.vec(lt->b);
+    lt->d_in = r.one<int>();
+    lt->d_out = r.one<int>();
+    lt->is_trained = r.one<bool>();
+    FAISS_THROW_IF_NOT(lt->d_in >= 0 && lt->d_out >= 0);
+    FAISS_THROW_IF_NOT(lt->A.size() >= (size_t)lt->d_in * lt->d_out);
+    FAISS_THROW_IF_NOT(!lt->have_bias || lt->b.size() >= (size_t)lt->d_out);
+    lt->set_is_orthonormal();
+    return lt.release();
+}
+
 void write_ivf_header(const IndexIVF* ivf, Writer& w) {
     write_header(ivf, w);
     w.one<size_t>(ivf->nlist);
@@ -515,6 +591,13 @@ void write_index_impl(const Index* idx, Writer& w) {
         write_index_impl(rf->base_index, w);
         write_index_impl(rf->refine_index, w);
         w.one<float>(rf->k_factor);
+    } else if (auto pt = dynamic_cast<const IndexPreTransform*>(idx)) {
+        // faiss/impl/index_write.cpp:725-735
+        w.one(fourcc("IxPT"));
+        write_header(pt, w);
+        w.one<int>((int)pt->chain.size());
+        for (auto* t : pt->chain) write_vt(t, w);
+        write_index_impl(pt->index, w);
     } else {
         FAISS_THROW_MSG("don't know how to serialize this type of index");
     }
@@ -651,9 +734,43 @@ Index* read_index_impl(Reader& r, int io_flags) {
         rf->k_factor = r.one<float>();
         return rf.release();
     }
+    if (h == fourcc("IxPT")) {
+        // faiss/impl/index_read.cpp:893-907
+        auto pt = std::make_unique<IndexPreTransform>();
+        pt->own_fields = true;
+        apply_header(pt.get(), read_header(r));
+        const int nt = r.one<int>();
+        FAISS_THROW_IF_NOT_MSG(nt >= 0 && nt < 1024, "IxPT: corrupt transform count");
+        for (int i = 0; i < nt; i++) pt->chain.push_back(read_vt(r));
+        pt->index = read_index_impl(r, io_flags);
+        FAISS_THROW_IF_NOT_MSG(pt->index, "IxPT: sub-index missing");
+        pt->device = pt->index->device;
+        return pt.release();
+    }
     FAISS_THROW_MSG("Index type " + fourcc_str(h) + " not supported on this path");
 }
 }  // namespace
+
+void write_VectorTransform(const VectorTransform* vt, const char* fname) {
+    AtomicFile f(fname);
+    Writer w{f.f};
+    write_vt(vt, w);
+    f.commit();
+}
+VectorTransform* read_VectorTransform(const char* fname) {
+    FILE* f = fopen(fname, "rb");
+    FAISS_THROW_IF_NOT_MSG(f, std::string("could not open ") + fname + " for reading");
+    VectorTransform* vt = nullptr;
+    try {
+        Reader r{f, fname};
+        vt = read_vt(r);
+    } catch (...) {
+        fclose(f);
+        throw;
+    }
+    fclose(f);
+    return vt;
+}
 
 void write_index(const Index* idx, FILE* f) {
     Writer w{f};
@@ -703,7 +820,77 @@ namespace {
 Index* factory_plain(int d, const std::string& s, MetricType metric);
 }
 
+namespace {
+// faiss/index_factory.cpp:160-208 (parse_VectorTransform): OPQ{M}[_{d_out}],
+// PCA[W][R]{d_out}, RR{d_out}.  nullptr when `tok` is none of them.  The
+// result is untrained; its train() throws (training is not served).
+VectorTransform* factory_transform(const std::string& tok, int d) {
+    auto number = [&](size_t pos, size_t* end) {
+        size_t p = pos;
+        while (p < tok.size() && isdigit((unsigned char)tok[p])) p++;
+        *end = p;
+        return p > pos ? (int)std::stol(tok.substr(pos, p - pos)) : -1;
+    };
+    size_t e = 0;
+    if (tok.rfind("OPQ", 0) == 0) {
+        const int M = number(3, &e);
+        int d_out = d;
+        if (M < 1) return nullptr;
+        if (e < tok.size() && tok[e] == '_') {
+            d_out = number(e + 1, &e);
+            if (d_out < 1) return nullptr;
+        }
+        return e == tok.size() ? new OPQMatrix(d, M, d_out) : nullptr;
+    }
+    if (tok.rfind("PCA", 0) == 0) {
+        size_t p = 3;
+        const bool white = p < tok.size() && tok[p] == 'W';
+        p += white;
+        const bool rot = p < tok.size() && tok[p] == 'R';
+        p += rot;
+        const int d_out = number(p, &e);
+        if (d_out < 1 || e != tok.size()) return nullptr;
+        return new PCAMatrix(d, d_out, white ? -0.5f : 0.f, rot);
+    }
+    if (tok.rfind("RR", 0) == 0) {
+        const int d_out = tok.size() == 2 ? d : number(2, &e);
+        if (d_out < 1 || (tok.size() > 2 && e != tok.size())) return nullptr;
+        return new RandomRotationMatrix(d, d_out);
+    }
+    return nullptr;
+}
+Index* factory_no_transform(int d, const char* description, MetricType metric);
+}  // namespace
+
 Index* index_factory(int d, const char* description, MetricType metric) {
+    // faiss/index_factory.cpp:820-870: leading comma-separated transforms
+    std::string s(description);
+    std::vector<std::unique_ptr<VectorTransform>> vts;
+    int dcur = d;
+    for (;;) {
+        const size_t comma = s.find(',');
+        if (comma == std::string::npos) break;
+        std::unique_ptr<VectorTransform> vt(factory_transform(s.substr(0, comma), dcur));
+        if (!vt) break;
+        dcur = vt->d_out;
+        vts.push_back(std::move(vt));
+        s.erase(0, comma + 1);
+    }
+    if (vts.empty()) return factory_no_transform(d, description, metric);
+    std::unique_ptr<Index> base(factory_no_transform(dcur, s.c_str(), metric));
+    auto pt = std::make_unique<IndexPreTransform>(base.get());
+    pt->own_fields = true;
+    base.release();
+    while (!vts.empty()) {
+        pt->prepend_transform(vts.back().get());
+        vts.back().release();
+        vts.pop_back();
+    }
+    return pt.release();
+}
+
+namespace {
+Index* factory_no_transform(int d, const char* description, MetricType metric) {
     // faiss/index_factory.cpp:700-716: "<base>,RFlat" / "<base>,Refine(<desc>)"
     // with k_factor 1.  Only a flat refine index is served, so both spellings
     // give an IndexRefineFlat (what the reference's reader makes of either).
@@ -725,6 +912,7 @@ Index* index_factory(int d, const char* description, MetricType metric) {
     rf->own_fields = true;
     return rf.release();
 }
+}  // namespace
 
 namespace {
 Index* factory_plain(int d, const std::string& s_in, MetricType metric) {

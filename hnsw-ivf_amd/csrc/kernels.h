@@ -566,5 +566,22 @@ void flat_range_direct(const float* x, int64_t nx, int ldx, const float* y, int6
                        int d, int metric_l2, float radius, const uint8_t* selm, uint32_t* counts,
                        const uint64_t* offsets, float* outD, int64_t* outI, hipStream_t s);
 
+// Linear vector transforms (kernels_transform.hip; the front end of
+// IndexPreTransform).  y[i][o] = b[o] + sum_j A[o][j] x[i][j]: x [n][ldx],
+// A [d_out][d_in] row-major, b [d_out] or nullptr, y [n][ldy] with the columns
+// d_out .. ldy - 1 written as zero.  fp32 MFMA in an evaluation order that
+// depends on (d_in, o) alone (file header), so a row's result does not change
+// with the batch around it.  variant: 0 = by n, 1 = the 128-row tile, 2 = the
+// 32-row tile (same bits; measurements only).  x and y must not overlap.
+constexpr int kTransformMaxDim = 65536;
+constexpr int kTransformNarrowRows = 32;  // n <= this: the 32-row tile
+void linear_transform(const float* x, int64_t n, int ldx, const float* A, int d_in, int d_out,
+                      const float* b, float* y, int ldy, hipStream_t s, int variant = 0);
+// x[i][j] = sum_o A[o][j] (y[i][o] - b[o]): y [n][ldy], x [n][ldx] with the
+// columns d_in .. ldx - 1 written as zero; the same order over o.
+void linear_transform_transposed(const float* y, int64_t n, int ldy, const float* A, int d_in,
+                                 int d_out, const float* b, float* x, int ldx, hipStream_t s,
+                                 int variant = 0);
+
 }  // namespace kern
 }  // namespace faiss_amd

@@ -93,6 +93,19 @@ using faiss_amd::IndexRefine;
 using faiss_amd::IndexRefineFlat;
 using faiss_amd::IndexRefineSearchParameters;
 
+// faiss/VectorTransform.h, faiss/IndexPreTransform.h, faiss/IVFlib.h
+using faiss_amd::extract_index_ivf;
+using faiss_amd::IndexPreTransform;
+using faiss_amd::LinearTransform;
+using faiss_amd::OPQMatrix;
+using faiss_amd::PCAMatrix;
+using faiss_amd::RandomRotationMatrix;
+using faiss_amd::read_VectorTransform;
+using faiss_amd::SearchParametersPreTransform;
+using faiss_amd::try_extract_index_ivf;
+using faiss_amd::VectorTransform;
+using faiss_amd::write_VectorTransform;
+
 // faiss/IndexShardsIVF.h
 using faiss_amd::IndexShardsIVF;
 

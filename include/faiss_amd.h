@@ -1067,6 +1067,161 @@ struct IndexRefineFlat : IndexRefine {
     IndexRefineFlat();
 };
 
+// ---------------------------------------------------------------- transforms
+// faiss/VectorTransform.h:25-66.  Host entry points (apply, apply_noalloc,
+// reverse_transform) take host pointers and are synchronous; the *_device
+// forms take device rows of leading dimension ldx / ldxt (>= d_in / d_out; the
+// columns past the row length are written as zero) and queue on `stream`.
+struct VectorTransform {
+    int d_in, d_out;
+    bool is_trained = true;
+    explicit VectorTransform(int d_in = 0, int d_out = 0) : d_in(d_in), d_out(d_out) {}
+    virtual ~VectorTransform() = default;
+    virtual void train(idx_t n, const float* x);
+    float* apply(idx_t n, const float* x) const;  // new float[n * d_out]
+    virtual void apply_noalloc(idx_t n, const float* x, float* xt) const;
+    virtual void reverse_transform(idx_t n, const float* xt, float* x) const;
+    virtual void apply_device(idx_t n, const float* x, int ldx, float* xt, int ldxt,
+                              hipStream_t stream) const = 0;
+    virtual void reverse_device(idx_t n, const float* xt, int ldxt, float* x, int ldx,
+                                hipStream_t stream) const;
+    // upload changed parameters (A, b) to the current device
+    virtual void sync_device() const {}
+};
+
+// faiss/VectorTransform.h:71-113: xt = A x + b on kern::linear_transform
+// (kernels_transform.hip; the evaluation order is a function of d_in alone,
+// so a vector transforms to the same bits in any batch).  A and b are public,
+// as in the reference: fill them, set is_trained, and the next host call or
+// sync_device() uploads them (a device call uses the last upload).
+struct LinearTransform : VectorTransform {
+    bool have_bias;
+    bool is_orthonormal = false;
+    std::vector<float> A;  // [d_out][d_in]
+    std::vector<float> b;  // [d_out]
+    bool verbose = false;
+    explicit LinearTransform(int d_in = 0, int d_out = 0, bool have_bias = false);
+    void apply_device(idx_t n, const float* x, int ldx, float* xt, int ldxt,
+                      hipStream_t stream) const override;
+    // x = A^T (xt - b) when A is orthonormal; throws otherwise
+    void reverse_transform(idx_t n, const float* xt, float* x) const override;
+    void reverse_device(idx_t n, const float* xt, int ldxt, float* x, int ldx,
+                        hipStream_t stream) const override;
+    void transform_transpose(idx_t n, const float* y, float* x) const;
+    void transpose_device(idx_t n, const float* y, int ldy, float* x, int ldx,
+                          hipStream_t stream) const;
+    // faiss/VectorTransform.cpp:240-284: |A A^T - I| <= 4e-5 elementwise
+    void set_is_orthonormal();
+    void sync_device() const override;
+
+   protected:
+    // training of the named subclasses needs an SVD / eigensolver / QR
+    [[noreturn]] void no_training(const char* what) const;
+    mutable std::mutex mu_;
+    mutable DeviceBuffer d_A_, d_b_;
+    mutable std::vector<float> up_A_, up_b_;  // what d_A_ / d_b_ hold
+    mutable bool uploaded_ = false;
+};
+
+// The named transforms are data carriers: they hold the reference's public
+// fields (files round-trip) and apply as the LinearTransform they are; their
+// training is not served and throws unless already trained.
+struct RandomRotationMatrix : LinearTransform {  // faiss/VectorTransform.h:115-128
+    explicit RandomRotationMatrix(int d_in = 0, int d_out = 0) : LinearTransform(d_in, d_out) {}
+    void init(int seed);  // throws: needs the reference's QR
+    void train(idx_t n, const float* x) override;
+};
+struct PCAMatrix : LinearTransform {  // faiss/VectorTransform.h:131-185
+    float eigen_power;
+    float epsilon = 0;
+    bool random_rotation;
+    size_t max_points_per_d = 1000;
+    int balanced_bins = 0;
+    std::vector<float> mean, eigenvalues, PCAMat;
+    explicit PCAMatrix(int d_in = 0, int d_out = 0, float eigen_power = 0,
+                       bool random_rotation = false);
+    void train(idx_t n, const float* x) override;
+};
+struct OPQMatrix : LinearTransform {  // faiss/VectorTransform.h:232-253
+    int M;
+    int niter = 50, niter_pq = 4, niter_pq_0 = 40;
+    size_t max_train_points = 256 * 256;
+    bool verbose = false;
+    explicit OPQMatrix(int d = 0, int M = 1, int d2 = -1);
+    void train(idx_t n, const float* x) override;
+};
+
+// faiss/IndexPreTransform.h:16-19
+struct SearchParametersPreTransform : SearchParameters {
+    SearchParameters* index_params = nullptr;  // not owned
+};
+
+// faiss/IndexPreTransform.h:23-110: vectors go through `chain` (GPU, between
+// two scratch buffers of the index) into the padded query rows of `index`,
+// without visiting the host.  d = the first transform's d_in.
+struct IndexPreTransform : Index {
+    std::vector<VectorTransform*> chain;
+    Index* index = nullptr;
+    bool own_fields = false;  // chain and index deleted with this object
+
+    explicit IndexPreTransform(Index* index);
+    IndexPreTransform();
+    IndexPreTransform(VectorTransform* ltrans, Index* index);
+    ~IndexPreTransform() override;
+
+    void prepend_transform(VectorTransform* ltrans);
+    // trains the sub-index on transformed data; an untrained transform's own
+    // train() is asked first (the named ones throw: training is not served)
+    void train(idx_t n, const float* x) override;
+    void add(idx_t n, const float* x) override;
+    void add_with_ids(idx_t n, const float* x, const idx_t* xids) override;
+    void reset() override;
+    size_t remove_ids(const IDSelector& sel) override;
+    void search_device(idx_t n, const float* x, int ldx, idx_t k, float* distances,
+                       idx_t* labels, const SearchParameters* params,
+                       hipStream_t stream) const override;
+    void assign_device(idx_t n, const float* x, int ldx, int k, float* distances,
+                       int32_t* labels, const SearchParameters* params,
+                       hipStream_t stream) const override;
+    void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result,
+                      const SearchParameters* params = nullptr) const override;
+    void reconstruct(idx_t key, float* recons) const override;
+    void reconstruct_n(idx_t i0, idx_t ni, float* recons) const override;
+    void search_and_reconstruct(idx_t n, const float* x, idx_t k, float* distances,
+                                idx_t* labels, float* recons,
+                                const SearchParameters* params = nullptr) const;
+    // host rows through the chain: new float[n * index->d] (the caller's own
+    // x when the chain is empty, as in the reference) / into xt
+    const float* apply_chain(idx_t n, const float* x) const;
+    void apply_chain_noalloc(idx_t n, const float* x, float* xt) const;
+    void reverse_chain(idx_t n, const float* xt, float* x) const;
+    // device rows through the chain into index scratch: [n][index->ld()],
+    // valid until the next call on this index (x itself for an empty chain)
+    const float* apply_chain_device(idx_t n, const float* x, int ldx, int* ldxt,
+                                    hipStream_t stream) const;
+    void sync_device() const override;
+    void fold_device_stats() const override;
+    uint64_t content_version() const override {
+        return version_.load() + (index ? index->content_version() : 0);
+    }
+
+   protected:
+    mutable std::recursive_mutex mu_;
+    mutable StreamOrder order_;
+    mutable DeviceBuffer s_t0_, s_t1_, s_in_;
+};
+
+// faiss/IVFlib.cpp:62-83: the IndexIVF inside an IndexPreTransform /
+// IndexRefine wrapper (nullptr / throw when there is none)
+const IndexIVF* try_extract_index_ivf(const Index* index);
+IndexIVF* try_extract_index_ivf(Index* index);
+const IndexIVF* extract_index_ivf(const Index* index);
+IndexIVF* extract_index_ivf(Index* index);
+
+// faiss/index_io.h:66-69
+void write_VectorTransform(const VectorTransform* vt, const char* fname);
+VectorTransform* read_VectorTransform(const char* fname);
+
 // ---------------------------------------------------------------- shards
 // faiss/IndexShardsIVF.h:19-40 — shards sharing one coarse quantizer.
 struct IndexShardsIVF : Index {

@@ -260,6 +260,161 @@ int faiss_amd_IndexRefineSearchParameters_new(
         FaissSearchParameters** p_sp);
 void faiss_amd_IndexRefineSearchParameters_free(FaissSearchParameters* obj);
 
+/* ---------------- VectorTransform (c_api/VectorTransform_c.h) ----------------
+ * Linear transforms applied on the GPU (kernels_transform.hip).  Host
+ * pointers; a transformed vector has the same bits in any batch.  Training
+ * of the named transforms is not served: _train fails with the FaissException
+ * code unless the transform is already trained. */
+typedef struct FaissVectorTransform_H FaissVectorTransform;
+typedef struct FaissVectorTransform_H FaissLinearTransform;
+typedef struct FaissVectorTransform_H FaissRandomRotationMatrix;
+typedef struct FaissVectorTransform_H FaissPCAMatrix;
+typedef struct FaissVectorTransform_H FaissOPQMatrix;
+typedef struct FaissVectorTransform_H FaissITQMatrix;
+typedef struct FaissVectorTransform_H FaissITQTransform;
+typedef struct FaissVectorTransform_H FaissRemapDimensionsTransform;
+typedef struct FaissVectorTransform_H FaissNormalizationTransform;
+typedef struct FaissVectorTransform_H FaissCenteringTransform;
+void faiss_VectorTransform_free(FaissVectorTransform* obj);              /* :25 */
+int faiss_VectorTransform_is_trained(const FaissVectorTransform*);      /* :28 */
+int faiss_VectorTransform_d_in(const FaissVectorTransform*);            /* :31 */
+int faiss_VectorTransform_d_out(const FaissVectorTransform*);           /* :34 */
+int faiss_VectorTransform_train(FaissVectorTransform* vt, idx_t n, const float* x); /* :42 */
+/* :51-72.  apply returns new float[n * d_out] (NULL on failure); the void
+ * ones leave their message for faiss_get_last_error() when they fail */
+float* faiss_VectorTransform_apply(const FaissVectorTransform* vt, idx_t n, const float* x);
+void faiss_VectorTransform_apply_noalloc(
+        const FaissVectorTransform* vt,
+        idx_t n,
+        const float* x,
+        float* xt);
+void faiss_VectorTransform_reverse_transform(
+        const FaissVectorTransform* vt,
+        idx_t n,
+        const float* xt,
+        float* x);
+/* the same two with a return code, and the class name of a transform */
+int faiss_amd_VectorTransform_apply_noalloc(
+        const FaissVectorTransform* vt,
+        idx_t n,
+        const float* x,
+        float* xt);
+int faiss_amd_VectorTransform_reverse_transform(
+        const FaissVectorTransform* vt,
+        idx_t n,
+        const float* xt,
+        float* x);
+const char* faiss_amd_VectorTransform_type(const FaissVectorTransform* vt);
+void faiss_LinearTransform_free(FaissLinearTransform* obj);              /* :76 */
+void faiss_LinearTransform_transform_transpose(                          /* :80 */
+        const FaissLinearTransform* vt,
+        idx_t n,
+        const float* y,
+        float* x);
+void faiss_LinearTransform_set_is_orthonormal(FaissLinearTransform* vt); /* :87 */
+int faiss_LinearTransform_have_bias(const FaissLinearTransform*);        /* :90 */
+int faiss_LinearTransform_is_orthonormal(const FaissLinearTransform*);   /* :93 */
+/* not in the reference C API (its LinearTransform has no C constructor): a
+ * transform to fill.  _set copies A [d_out][d_in] and b [d_out] (NULL: no
+ * bias), marks it trained and runs set_is_orthonormal; _A / _b look at the
+ * stored vectors */
+int faiss_amd_LinearTransform_new(FaissLinearTransform** p_vt, int d_in, int d_out, int have_bias);
+int faiss_amd_LinearTransform_set(FaissLinearTransform* vt, const float* A, const float* b);
+int faiss_amd_LinearTransform_A(const FaissLinearTransform* vt, const float** A, size_t* n);
+int faiss_amd_LinearTransform_b(const FaissLinearTransform* vt, const float** b, size_t* n);
+void faiss_RandomRotationMatrix_free(FaissRandomRotationMatrix* obj);    /* :96 */
+int faiss_RandomRotationMatrix_new_with(FaissRandomRotationMatrix** p_vt, int d_in, int d_out);
+void faiss_PCAMatrix_free(FaissPCAMatrix* obj);                          /* :104 */
+int faiss_PCAMatrix_new_with(                                            /* :106 */
+        FaissPCAMatrix** p_vt,
+        int d_in,
+        int d_out,
+        float eigen_power,
+        int random_rotation);
+float faiss_PCAMatrix_eigen_power(const FaissPCAMatrix*);                /* :114 */
+int faiss_PCAMatrix_random_rotation(const FaissPCAMatrix*);              /* :117 */
+void faiss_OPQMatrix_free(FaissOPQMatrix* obj);                          /* :137 */
+int faiss_OPQMatrix_new_with(FaissOPQMatrix** p_vt, int d, int M, int d2); /* :139 */
+int faiss_OPQMatrix_verbose(const FaissOPQMatrix*);                      /* :141-143 */
+void faiss_OPQMatrix_set_verbose(FaissOPQMatrix*, int);
+int faiss_OPQMatrix_niter(const FaissOPQMatrix*);
+void faiss_OPQMatrix_set_niter(FaissOPQMatrix*, int);
+int faiss_OPQMatrix_niter_pq(const FaissOPQMatrix*);
+void faiss_OPQMatrix_set_niter_pq(FaissOPQMatrix*, int);
+/* :119-167: kinds this path does not serve; the constructors return the
+ * FaissException code with a message naming the kind */
+int faiss_ITQMatrix_new_with(FaissITQMatrix** p_vt, int d);
+int faiss_ITQTransform_new_with(FaissITQTransform** p_vt, int d_in, int d_out, int do_pca);
+int faiss_RemapDimensionsTransform_new_with(
+        FaissRemapDimensionsTransform** p_vt,
+        int d_in,
+        int d_out,
+        int uniform);
+int faiss_NormalizationTransform_new_with(FaissNormalizationTransform** p_vt, int d, float norm);
+int faiss_CenteringTransform_new_with(FaissCenteringTransform** p_vt, int d);
+/* the kernel alone on device pointers: out [n][ld_out] = in [n][ld_in] through
+ * A [d_out][d_in] and b [d_out] (or NULL); transposed != 0: out = A^T (in - b).
+ * Columns past the row length of out are written as zero.  variant 0 picks
+ * the tile by n, 1 / 2 force the 128- / 32-row tile (same bits) */
+int faiss_amd_linear_transform_device(
+        const float* in,
+        idx_t n,
+        int ld_in,
+        const float* A,
+        int d_in,
+        int d_out,
+        const float* b,
+        float* out,
+        int ld_out,
+        int transposed,
+        int variant,
+        void* stream);
+
+/* ---------------- IndexPreTransform (c_api/IndexPreTransform_c.h) ---------------- */
+typedef struct FaissIndex_H FaissIndexPreTransform;
+void faiss_IndexPreTransform_free(FaissIndexPreTransform* obj);               /* :24 */
+FaissIndexPreTransform* faiss_IndexPreTransform_cast(FaissIndex* index);      /* :25 */
+FaissIndex* faiss_IndexPreTransform_index(const FaissIndexPreTransform*);     /* :27 */
+int faiss_IndexPreTransform_own_fields(const FaissIndexPreTransform*);        /* :28 */
+void faiss_IndexPreTransform_set_own_fields(FaissIndexPreTransform*, int);
+int faiss_IndexPreTransform_new(FaissIndexPreTransform** p_index);            /* :30 */
+int faiss_IndexPreTransform_new_with(FaissIndexPreTransform** p_index, FaissIndex* index);
+int faiss_IndexPreTransform_new_with_transform(                               /* :36 */
+        FaissIndexPreTransform** p_index,
+        FaissVectorTransform* ltrans,
+        FaissIndex* index);
+int faiss_IndexPreTransform_prepend_transform(                                /* :41 */
+        FaissIndexPreTransform* index,
+        FaissVectorTransform* ltrans);
+/* not in the reference C API: the chain, apply_chain / reverse_chain on host
+ * rows (xt [n][sub-index d], x [n][d]), search_and_reconstruct, and
+ * SearchParametersPreTransform (index_params not owned, may be NULL) */
+int faiss_amd_IndexPreTransform_chain_size(const FaissIndexPreTransform*);
+FaissVectorTransform* faiss_amd_IndexPreTransform_chain_at(const FaissIndexPreTransform*, int t);
+int faiss_amd_IndexPreTransform_apply_chain(
+        const FaissIndexPreTransform* index,
+        idx_t n,
+        const float* x,
+        float* xt);
+int faiss_amd_IndexPreTransform_reverse_chain(
+        const FaissIndexPreTransform* index,
+        idx_t n,
+        const float* xt,
+        float* x);
+int faiss_amd_IndexPreTransform_search_and_reconstruct(
+        const FaissIndexPreTransform* index,
+        idx_t n,
+        const float* x,
+        idx_t k,
+        const FaissSearchParameters* params,
+        float* distances,
+        idx_t* labels,
+        float* recons);
+int faiss_amd_SearchParametersPreTransform_new(
+        FaissSearchParameters* index_params,
+        FaissSearchParameters** p_sp);
+void faiss_amd_SearchParametersPreTransform_free(FaissSearchParameters* obj);
+
 /* ---------------- IndexIVF (c_api/IndexIVF_c.h) ---------------- */
 size_t faiss_IndexIVF_nlist(const FaissIndexIVF*);              /* :59 */
 size_t faiss_IndexIVF_nprobe(const FaissIndexIVF*);             /* :61 */
