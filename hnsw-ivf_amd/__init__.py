@@ -310,6 +310,16 @@ def _declare(L):
         "faiss_amd_IndexPreTransform_search_and_reconstruct": (C.c_int, [_P, _I64, _P, _I64, _P,
                                                                          _P, _P, _P]),
         "faiss_amd_SearchParametersPreTransform_new": (C.c_int, [_P, C.POINTER(_P)]),
+        "faiss_IndexPQ_new_with": (C.c_int, [C.POINTER(_P), C.c_int64, C.c_size_t, C.c_size_t, C.c_int]),
+        "faiss_amd_IndexPQ_info": (C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+        "faiss_amd_IndexPQ_set_search_type": (C.c_int, [_P, C.c_int]),
+        "faiss_amd_IndexPQ_pq_centroids": (None, [_P, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t)]),
+        "faiss_amd_IndexPQ_codes": (None, [_P, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
+        "faiss_amd_IndexPQ_set_content": (C.c_int, [_P, C.c_void_p, C.c_int64, C.c_void_p]),
+        "faiss_amd_SearchParametersPQ_new": (C.c_int, [C.c_int, C.c_int, _P, C.POINTER(_P)]),
+        "faiss_amd_SearchParametersPQ_free": (None, [_P]),
+        "faiss_amd_indexPQ_stats": (None, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "faiss_amd_indexPQ_stats_reset": (None, []),
         "faiss_amd_SearchParametersPreTransform_free": (None, [_P]),
     }
     for name, (res, args) in sig.items():
@@ -928,6 +938,99 @@ class IndexIVFScalarQuantizer(IndexIVF):
             self.h, x.shape[0], _ptr(x), _ptr(ids) if ids is not None else None, _ptr(pre)))
 
 
+# faiss/IndexPQ.h Search_type_t
+ST_PQ, ST_HE, ST_generalized_HE, ST_SDC, ST_polysemous, ST_polysemous_generalize = range(6)
+
+
+class IndexPQ(Index):
+    """faiss.IndexPQ: a flat array of product-quantizer codes (nbits 4..8),
+    searched exhaustively on the GPU with the asymmetric distance (ST_PQ)."""
+
+    def __init__(self, d=None, M=None, nbits=8, metric=METRIC_L2, handle=None, owner=None):
+        if handle is None:
+            p = C.c_void_p()
+            _check(lib().faiss_IndexPQ_new_with(C.byref(p), d, M, nbits, metric))
+            handle = p
+        super().__init__(handle, owner)
+
+    def pq_info(self):
+        M, nb, cs, st = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int()
+        _check(lib().faiss_amd_IndexPQ_info(self.h, C.byref(M), C.byref(nb), C.byref(cs),
+                                            C.byref(st)))
+        return dict(M=M.value, nbits=nb.value, code_size=cs.value, search_type=st.value)
+
+    @property
+    def code_size(self):
+        return self.pq_info()["code_size"]
+
+    @property
+    def search_type(self):
+        return self.pq_info()["search_type"]
+
+    @search_type.setter
+    def search_type(self, v):
+        _check(lib().faiss_amd_IndexPQ_set_search_type(self.h, int(v)))
+
+    @property
+    def pq_centroids(self):
+        """A copy of pq.centroids, [M][ksub][dsub]."""
+        p, n = C.POINTER(C.c_float)(), C.c_size_t(0)
+        lib().faiss_amd_IndexPQ_pq_centroids(self.h, C.byref(p), C.byref(n))
+        info = self.pq_info()
+        return np.ctypeslib.as_array(p, shape=(n.value,)).reshape(
+            info["M"], 1 << info["nbits"], self.d // info["M"]).copy()
+
+    @property
+    def codes(self):
+        """A copy of the code array, [ntotal][code_size] uint8."""
+        p, n = C.POINTER(C.c_uint8)(), C.c_size_t(0)
+        lib().faiss_amd_IndexPQ_codes(self.h, C.byref(p), C.byref(n))
+        if n.value == 0:
+            return np.zeros((0, self.code_size), np.uint8)
+        return np.ctypeslib.as_array(p, shape=(n.value,)).reshape(-1, self.code_size).copy()
+
+    def set_content(self, centroids=None, codes=None):
+        """Assign pq.centroids ([M][ksub][dsub]; the index becomes trained)
+        and / or the whole code array ([n][code_size] uint8; ntotal = n)."""
+        info = self.pq_info()
+        c = k = None
+        n = 0
+        if centroids is not None:
+            c = np.ascontiguousarray(centroids, dtype=np.float32)
+            assert c.size == self.d << info["nbits"]
+        if codes is not None:
+            k = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, info["code_size"])
+            n = k.shape[0]
+        _check(lib().faiss_amd_IndexPQ_set_content(
+            self.h, c.ctypes.data if c is not None else None, n,
+            k.ctypes.data if k is not None else None))
+
+
+class SearchParametersPQ:
+    """faiss.SearchParametersPQ: the search type of the call (ST_PQ is served)."""
+
+    def __init__(self, search_type=ST_PQ, polysemous_ht=0, sel=None):
+        p = C.c_void_p()
+        _check(lib().faiss_amd_SearchParametersPQ_new(int(search_type), int(polysemous_ht),
+                                                      sel.h if sel else None, C.byref(p)))
+        self.h = p
+        self._sel = sel
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().faiss_amd_SearchParametersPQ_free(self.h)
+            self.h = None
+
+
+def indexPQ_stats(reset=False):
+    """The global faiss.indexPQ_stats as a dict (nq, ncode)."""
+    if reset:
+        lib().faiss_amd_indexPQ_stats_reset()
+    nq, nc = C.c_size_t(), C.c_size_t()
+    lib().faiss_amd_indexPQ_stats(C.byref(nq), C.byref(nc))
+    return dict(nq=nq.value, ncode=nc.value)
+
+
 class IndexRefineFlat(Index):
     """faiss.IndexRefineFlat: searches k * k_factor candidates in base_index and
     re-ranks them with exact distances from a flat copy of the vectors."""
@@ -1376,7 +1479,7 @@ def _wrap(h, owner=None):
     cls = {"IndexIVFPQ": IndexIVFPQ, "IndexIVFFlat": IndexIVFFlat,
            "IndexIVFScalarQuantizer": IndexIVFScalarQuantizer,
            "IndexHNSWFlat": IndexHNSWFlat, "IndexFlat": IndexFlat,
-           "IndexRefineFlat": IndexRefineFlat,
+           "IndexRefineFlat": IndexRefineFlat, "IndexPQ": IndexPQ,
            "IndexPreTransform": IndexPreTransform}.get(t)
     if cls is None:
         return Index(h, owner)

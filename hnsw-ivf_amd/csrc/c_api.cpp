@@ -58,6 +58,9 @@ const IndexIVF* IVF(const FaissIndex* p) {
 struct PreTransformParamsC {
     SearchParametersPreTransform pt;
 };
+struct PQParamsC {
+    SearchParametersPQ pq;
+};
 inline VectorTransform* VT(FaissVectorTransform* p) { return reinterpret_cast<VectorTransform*>(p); }
 inline const VectorTransform* VT(const FaissVectorTransform* p) {
     return reinterpret_cast<const VectorTransform*>(p);
@@ -131,6 +134,7 @@ static const SearchParameters* resolve_params(const FaissSearchParameters* p) {
     auto base = reinterpret_cast<const SearchParameters*>(p);
     if (dynamic_cast<const IndexRefineSearchParameters*>(base)) return base;
     if (dynamic_cast<const SearchParametersPreTransform*>(base)) return base;
+    if (dynamic_cast<const SearchParametersPQ*>(base)) return base;
     if (dynamic_cast<const SearchParametersHNSW*>(base)) return base;
     auto sp = reinterpret_cast<const SearchParamsC*>(p);
     return &sp->ivf;
@@ -425,6 +429,68 @@ void faiss_IndexFlat_xb(FaissIndexFlat* index, float** p_xb, size_t* p_size) {
     *p_xb = f->xb.data();
     *p_size = f->xb.size();
 }
+
+// ---------------- IndexPQ
+int faiss_IndexPQ_new_with(FaissIndexPQ** p_index, idx_t d, size_t M, size_t nbits,
+                           FaissMetricType metric) {
+    C_TRY* p_index = FX(new IndexPQ((int)d, M, nbits, (MetricType)metric));
+    C_CATCH
+}
+void faiss_IndexPQ_free(FaissIndexPQ* obj) { delete IX(obj); }
+FaissIndexPQ* faiss_IndexPQ_cast(FaissIndex* index) {
+    return dynamic_cast<IndexPQ*>(IX(index)) ? index : nullptr;
+}
+static IndexPQ* PQm(const FaissIndex* i) {
+    auto r = dynamic_cast<IndexPQ*>(const_cast<Index*>(IX(i)));
+    FAISS_THROW_IF_NOT_MSG(r, "not an IndexPQ");
+    return r;
+}
+int faiss_amd_IndexPQ_info(const FaissIndexPQ* index, size_t* M, size_t* nbits, size_t* code_size,
+                           int* search_type) {
+    C_TRY auto pq = PQm(index);
+    *M = pq->pq.M;
+    *nbits = pq->pq.nbits;
+    *code_size = pq->code_size;
+    *search_type = (int)pq->search_type;
+    C_CATCH
+}
+int faiss_amd_IndexPQ_set_search_type(FaissIndexPQ* index, int search_type) {
+    C_TRY FAISS_THROW_IF_NOT(search_type >= 0 && search_type <= (int)IndexPQ::ST_polysemous_generalize);
+    PQm(index)->search_type = (IndexPQ::Search_type_t)search_type;
+    C_CATCH
+}
+void faiss_amd_IndexPQ_pq_centroids(FaissIndexPQ* index, float** p, size_t* n) {
+    auto pq = dynamic_cast<IndexPQ*>(IX(index));
+    *p = pq ? pq->pq.centroids.data() : nullptr;
+    *n = pq ? pq->pq.centroids.size() : 0;
+}
+void faiss_amd_IndexPQ_codes(FaissIndexPQ* index, uint8_t** p, size_t* n) {
+    auto pq = dynamic_cast<IndexPQ*>(IX(index));
+    *p = pq ? pq->codes.data() : nullptr;
+    *n = pq ? pq->codes.size() : 0;
+}
+int faiss_amd_IndexPQ_set_content(FaissIndexPQ* index, const float* centroids, idx_t n,
+                                  const uint8_t* codes) {
+    C_TRY PQm(index)->set_content(centroids, n, codes);
+    C_CATCH
+}
+int faiss_amd_SearchParametersPQ_new(int search_type, int polysemous_ht, FaissIDSelector* sel,
+                                     FaissSearchParameters** p_sp) {
+    C_TRY auto sp = new PQParamsC();
+    sp->pq.search_type = search_type;
+    sp->pq.polysemous_ht = polysemous_ht;
+    sp->pq.sel = reinterpret_cast<IDSelector*>(sel);
+    *p_sp = reinterpret_cast<FaissSearchParameters*>(sp);
+    C_CATCH
+}
+void faiss_amd_SearchParametersPQ_free(FaissSearchParameters* obj) {
+    delete reinterpret_cast<PQParamsC*>(obj);
+}
+void faiss_amd_indexPQ_stats(size_t* nq, size_t* ncode) {
+    *nq = indexPQ_stats.nq;
+    *ncode = indexPQ_stats.ncode;
+}
+void faiss_amd_indexPQ_stats_reset(void) { indexPQ_stats.reset(); }
 
 // ---------------- IndexRefineFlat (c_api/IndexFlat_c.h:89-107, IndexFlat_c.cpp:113-132)
 int faiss_IndexRefineFlat_new(FaissIndexRefineFlat** p_index, FaissIndex* base_index) {

@@ -23,6 +23,8 @@
 //             efSearch:int, dummy int), storage index         (:300-316,760-778)
 //   IxRF    = header, base index, refine index, k_factor:f32    (:744-752)
 //   IxPT    = header, nt:i32, nt VectorTransform records, sub-index (:725-735)
+//   IxPq    = header, PQ (d,M,nbits:size_t, centroids), codes:vec<u8>,
+//             search_type:i32, encode_signs:u8, polysemous_ht:i32 (:417-425)
 //   VectorTransform = rrot | Pcam + PCA fields | LTra, then have_bias:u8,
 //             A, b, d_in:i32, d_out:i32, is_trained:u8          (:92-153)
 //   vectors carry a size_t element-count prefix (faiss/impl/io_macros.h:62-67)
@@ -584,6 +586,18 @@ void write_index_impl(const Index* idx, Writer& w) {
         w.one<size_t>(sq->code_size);
         w.one<uint8_t>(sq->by_residual ? 1 : 0);
         write_invlists(sq->invlists.get(), w);
+    } else if (auto ipq = dynamic_cast<const IndexPQ*>(idx)) {
+        // faiss/impl/index_write.cpp:417-425
+        w.one(fourcc("IxPq"));
+        write_header(ipq, w);
+        w.one<size_t>(ipq->pq.d);
+        w.one<size_t>(ipq->pq.M);
+        w.one<size_t>(ipq->pq.nbits);
+        w.vec(ipq->pq.centroids);
+        w.vec(ipq->codes);
+        w.one<int32_t>((int32_t)ipq->search_type);
+        w.one<bool>(ipq->encode_signs);
+        w.one<int32_t>(ipq->polysemous_ht);
     } else if (auto rf = dynamic_cast<const IndexRefine*>(idx)) {
         // faiss/impl/index_write.cpp:744-752
         w.one(fourcc("IxRF"));
@@ -713,6 +727,26 @@ Index* read_index_impl(Reader& r, int io_flags) {
             if (pqi->is_trained && pqi->by_residual) pqi->precompute_table();
         }
         return ivf;
+    }
+    if (h == fourcc("IxPq") || h == fourcc("IxPo") || h == fourcc("IxPQ")) {
+        // faiss/impl/index_read.cpp:585-604
+        Header hd = read_header(r);
+        const size_t pd = r.one<size_t>(), M = r.one<size_t>(), nbits = r.one<size_t>();
+        FAISS_THROW_IF_NOT(pd == (size_t)hd.d);
+        auto ix = std::make_unique<IndexPQ>(hd.d, M, nbits, (MetricType)hd.metric);
+        apply_header(ix.get(), hd);
+        r.vec(ix->pq.centroids);
+        FAISS_THROW_IF_NOT(ix->pq.centroids.size() == pd * ((size_t)1 << nbits));
+        r.vec(ix->codes);
+        FAISS_THROW_IF_NOT(ix->codes.size() == (size_t)hd.ntotal * ix->code_size);
+        if (h != fourcc("IxPQ")) {
+            ix->search_type = (IndexPQ::Search_type_t)r.one<int32_t>();
+            ix->encode_signs = r.one<bool>();
+            ix->polysemous_ht = r.one<int32_t>();
+        }
+        // the two old tags stored INNER_PRODUCT while searching L2
+        if (h != fourcc("IxPq")) ix->metric_type = METRIC_L2;
+        return ix.release();
     }
     if (h == fourcc("IxRF")) {
         // faiss/impl/index_read.cpp:913-928: a flat refine index makes the
@@ -931,6 +965,18 @@ Index* factory_plain(int d, const std::string& s_in, MetricType metric) {
         FAISS_THROW_IF_NOT_MSG(rest.empty() || rest == ",Flat" || rest == "_Flat",
                                "unsupported HNSW description " + s);
         return new IndexHNSWFlat(d, M, metric);
+    }
+    if (s.rfind("PQ", 0) == 0 && s.size() > 2 && isdigit((unsigned char)s[2])) {
+        // faiss/index_factory.cpp:571-590 (IndexPQ): PQ{M}[x{nbits}]
+        size_t pos = 2;
+        const size_t M = (size_t)parse_int(pos);
+        size_t nbits = 8;
+        if (pos < s.size() && s[pos] == 'x') {
+            pos++;
+            nbits = (size_t)parse_int(pos);
+        }
+        FAISS_THROW_IF_NOT_MSG(pos == s.size(), "unsupported PQ spec " + s);
+        return new IndexPQ(d, M, nbits, metric);
     }
     FAISS_THROW_IF_NOT_MSG(s.rfind("IVF", 0) == 0, "unsupported index_factory string " + s);
     size_t pos = 3;

@@ -1576,16 +1576,7 @@ void IndexIVFPQ::train_encoder(idx_t n, const float* x, const idx_t* assign) {
             memcpy(ri, xi, sizeof(float) * d);
         }
     }
-    std::vector<float> sub((size_t)nt * pq.dsub), cent(pq.ksub * pq.dsub);
-    for (size_t m = 0; m < pq.M; m++) {
-        for (idx_t i = 0; i < nt; i++)
-            memcpy(sub.data() + (size_t)i * pq.dsub, resid.data() + (size_t)i * d + m * pq.dsub,
-                   sizeof(float) * pq.dsub);
-        kmeans_train((int)pq.dsub, nt, sub.data(), (int)pq.ksub, 25, 1234 + (int64_t)m,
-                     cent.data(), device, false);
-        memcpy(pq.centroids.data() + m * pq.ksub * pq.dsub, cent.data(),
-               sizeof(float) * pq.ksub * pq.dsub);
-    }
+    pq.train((size_t)nt, resid.data(), device);
     precompute_table();
     std::lock_guard<std::recursive_mutex> g(mu_);
     dirty_ = true;
@@ -1603,48 +1594,79 @@ void IndexIVFPQ::precompute_table() {
 void IndexIVFPQ::encode_vectors(idx_t n, const float* x, const idx_t* list_nos,
                                 uint8_t* codes) const {
     if (n <= 0) return;
-    DevGuard dg(device);
-    hipStream_t s = stream();
     const int ldx = ld();
-    // k_pq_encode writes one byte per index at a stride of roundup(M, 4)
-    // (nbits = 8: the device code stride); narrower indexes are packed below
-    const int cs = (int)roundup(pq.M, 4);
     std::vector<int32_t> a32(n);
     for (idx_t i = 0; i < n; i++) a32[i] = (int32_t)std::max<idx_t>(list_nos[i], 0);
     std::vector<float> cent((size_t)nlist * ldx, 0.f);
     if (by_residual)
         for (size_t l = 0; l < nlist; l++) quantizer->reconstruct(l, cent.data() + l * ldx);
+    pq.compute_codes_residual(x, codes, (size_t)n, a32.data(), by_residual ? cent.data() : nullptr,
+                              nlist, ldx, device);
+}
+
+// ProductQuantizer::train (faiss/impl/ProductQuantizer.cpp:215-285, the
+// default train_type): k-means per sub-space — this library's k-means, so
+// the codebooks are not the reference's
+void ProductQuantizer::train(size_t n, const float* x, int device) {
+    std::vector<float> sub(n * dsub), cent(ksub * dsub);
+    for (size_t m = 0; m < M; m++) {
+        for (size_t i = 0; i < n; i++)
+            memcpy(sub.data() + i * dsub, x + i * d + m * dsub, sizeof(float) * dsub);
+        kmeans_train((int)dsub, (idx_t)n, sub.data(), (int)ksub, 25, 1234 + (int64_t)m,
+                     cent.data(), device, false);
+        memcpy(centroids.data() + m * ksub * dsub, cent.data(), sizeof(float) * ksub * dsub);
+    }
+}
+
+void ProductQuantizer::compute_codes(const float* x, uint8_t* codes, size_t n, int device) const {
+    compute_codes_residual(x, codes, n, nullptr, nullptr, 0, 0, device);
+}
+
+void ProductQuantizer::compute_codes_residual(const float* x, uint8_t* codes, size_t n_,
+                                              const int32_t* assign, const float* cent,
+                                              size_t ncent, int ldc, int device) const {
+    const idx_t n = (idx_t)n_;
+    if (n <= 0) return;
+    DevGuard dg(device);
+    hipStream_t s = device_context(device).stream;
+    const int ldx = (int)roundup(d, 4);
+    const size_t code_size = (M * nbits + 7) / 8;
+    // k_pq_encode writes one byte per index at a stride of roundup(M, 4)
+    // (nbits = 8: the device code stride); narrower indexes are packed below
+    const int cs = (int)roundup(M, 4);
     DeviceBuffer bx, ba, bc, bp, bo;
     bx.reserve(sizeof(float) * n * ldx);
-    ba.reserve(sizeof(int32_t) * n);
-    bc.reserve(sizeof(float) * cent.size());
-    bp.reserve(sizeof(float) * pq.centroids.size());
+    bp.reserve(sizeof(float) * centroids.size());
     bo.reserve((size_t)n * cs);
     upload_rows(bx.as<float>(), ldx, x, (int)d, n, s);
-    HIP_CHECK(hipMemcpyAsync(ba.ptr, a32.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(bc.ptr, cent.data(), sizeof(float) * cent.size(),
+    if (cent) {
+        ba.reserve(sizeof(int32_t) * n);
+        bc.reserve(sizeof(float) * ncent * ldc);
+        HIP_CHECK(hipMemcpyAsync(ba.ptr, assign, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(bc.ptr, cent, sizeof(float) * ncent * ldc, hipMemcpyHostToDevice,
+                                 s));
+    }
+    HIP_CHECK(hipMemcpyAsync(bp.ptr, centroids.data(), sizeof(float) * centroids.size(),
                              hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(bp.ptr, pq.centroids.data(), sizeof(float) * pq.centroids.size(),
-                             hipMemcpyHostToDevice, s));
-    kern::pq_encode(bx.as<float>(), ldx, n, ba.as<int32_t>(),
-                    by_residual ? bc.as<float>() : nullptr, ldx, bp.as<float>(), (int)pq.M,
-                    (int)pq.ksub, (int)pq.dsub, bo.as<uint8_t>(), s);
+    kern::pq_encode(bx.as<float>(), ldx, n, cent ? ba.as<int32_t>() : nullptr,
+                    cent ? bc.as<float>() : nullptr, ldc, bp.as<float>(), (int)M, (int)ksub,
+                    (int)dsub, bo.as<uint8_t>(), s);
     std::vector<uint8_t> hc((size_t)n * cs);
     HIP_CHECK(hipMemcpyAsync(hc.data(), bo.ptr, hc.size(), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    if (pq.nbits == 8) {
+    if (nbits == 8) {
         for (idx_t i = 0; i < n; i++)
             memcpy(codes + (size_t)i * code_size, hc.data() + (size_t)i * cs, code_size);
         return;
     }
     // PQEncoderGeneric (faiss/impl/ProductQuantizer-inl.h:10-55): little-endian
     // bit stream, the last byte's top bits zero
-    const int nb = (int)pq.nbits;
+    const int nb = (int)nbits;
     for (idx_t i = 0; i < n; i++) {
         uint8_t* out = codes + (size_t)i * code_size;
         const uint8_t* in = hc.data() + (size_t)i * cs;
         memset(out, 0, code_size);
-        for (size_t m = 0; m < pq.M; m++) {
+        for (size_t m = 0; m < M; m++) {
             const size_t o = m * nb;
             const uint32_t v = (uint32_t)in[m] << (o & 7);
             out[o >> 3] |= (uint8_t)v;

@@ -322,6 +322,29 @@ bool ivfpq_lut_eligible(int M, int nbits, int code_stride, int ldx, int k);
 size_t ivfpq_lut_scratch_words(int64_t n);
 void ivfpq_lut_search(const ExactScanArgs& a, const IVFBuckets& b, int64_t max_items, int QT,
                       uint32_t* scratch, float* D, int64_t* I, hipStream_t s);
+// IndexPQ: exact k-NN over a flat array of packed PQ codes with the queries'
+// tables in LDS (kernels_pq_flat.hip; tables in global scratch when one does
+// not fit).  Rows are their own labels; D / I [n][k] sorted as the reference
+// heap leaves them, pads (FLT_MAX / -FLT_MAX, -1).  k <= kMaxKExact; k <=
+// PQ_FLAT_KSEL selects inside the scan, above it from dense distance rows.
+// The three scratch buffers grow on demand and are never shrunk.
+constexpr int PQ_FLAT_KSEL = 32;
+struct PQFlatArgs {
+    const float* x = nullptr;  // [n][ldx] queries
+    int ldx = 0, d = 0;
+    int64_t n = 0;
+    const float* pq_cent = nullptr;  // [M][1 << nbits][dsub]
+    int M = 0, dsub = 0, nbits = 8;
+    const uint8_t* codes = nullptr;  // [ntotal] rows of cs bytes, PQEncoderGeneric's bit stream
+    int cs = 0;                      // multiple of 4
+    int64_t ntotal = 0;
+    int k = 0, l2 = 1;
+};
+void pq_flat_search(const PQFlatArgs& a, DeviceBuffer& s_part, DeviceBuffer& s_tab,
+                    DeviceBuffer& s_dense, float* D, int64_t* I, hipStream_t s);
+// queries a work group holds tables for at this shape (*global_tables: they
+// do not fit the LDS and live in global scratch)
+int pq_flat_queries_per_group(const PQFlatArgs& a, bool* global_tables = nullptr);
 // exact top-k (reference heap semantics, label = col0 + column) of dense rows;
 // k > kMaxKExact runs with global scratch (required then)
 template <class OutIdx>

@@ -88,6 +88,12 @@ using faiss_amd::ProductQuantizer;
 using faiss_amd::IndexIVFScalarQuantizer;
 using faiss_amd::ScalarQuantizer;
 
+// faiss/IndexPQ.h
+using faiss_amd::IndexPQ;
+using faiss_amd::indexPQ_stats;
+using faiss_amd::IndexPQStats;
+using faiss_amd::SearchParametersPQ;
+
 // faiss/IndexRefine.h
 using faiss_amd::IndexRefine;
 using faiss_amd::IndexRefineFlat;

@@ -884,6 +884,15 @@ struct ProductQuantizer {
     void set_derived_values();
     // faiss/impl/ProductQuantizer.cpp:343-375: one packed code -> d floats
     void decode(const uint8_t* code, float* x) const;
+    // faiss/impl/ProductQuantizer.cpp:215-285 (default train_type): k-means per
+    // sub-space on `device` — this library's k-means, not parity-checked
+    void train(size_t n, const float* x, int device = 0);
+    // codes [n][(M nbits + 7) / 8]: first-minimum encoder on the GPU
+    // (kern::pq_encode), then PQEncoderGeneric's bit packing
+    void compute_codes(const float* x, uint8_t* codes, size_t n, int device = 0) const;
+    // the same on x_i - cent[assign[i]] (host rows cent [ncent][ldc]; null: x_i)
+    void compute_codes_residual(const float* x, uint8_t* codes, size_t n, const int32_t* assign,
+                                const float* cent, size_t ncent, int ldc, int device) const;
 };
 
 struct IndexIVFPQ : IndexIVF {
@@ -1003,6 +1012,70 @@ struct IndexIVFScalarQuantizer : IndexIVF {
                       const uint64_t* offs, float* D, idx_t* I, bool store_pairs,
                       hipStream_t s) const override;
     mutable DeviceBuffer d_trained_, d_cent_;
+};
+
+// ---------------------------------------------------------------- IndexPQ
+// faiss/IndexPQ.h:19-150 over IndexFlatCodes: the flat array of PQ codes,
+// searched exhaustively by kern::pq_flat_search (kernels_pq_flat.hip: the
+// queries' distance tables in LDS).  nbits 4..8; the asymmetric search
+// (ST_PQ) only — the polysemous / SDC / Hamming search types throw.
+struct SearchParametersPQ : SearchParameters {  // faiss/IndexPQ.h:152-156
+    int search_type = 0;  // IndexPQ::Search_type_t
+    int polysemous_ht = 0;
+};
+struct IndexPQStats {  // faiss/IndexPQ.h:160-171
+    size_t nq = 0, ncode = 0, n_hamming_pass = 0;
+    void reset() { *this = IndexPQStats(); }
+};
+extern IndexPQStats indexPQ_stats;
+
+struct IndexPQ : Index {
+    enum Search_type_t {
+        ST_PQ,
+        ST_HE,
+        ST_generalized_HE,
+        ST_SDC,
+        ST_polysemous,
+        ST_polysemous_generalize,
+    };
+    ProductQuantizer pq;
+    std::vector<uint8_t> codes;  // [ntotal][code_size] (IndexFlatCodes::codes)
+    size_t code_size = 0;
+    bool do_polysemous_training = false;
+    Search_type_t search_type = ST_PQ;
+    bool encode_signs = false;
+    int polysemous_ht = 0;
+
+    IndexPQ(int d, size_t M, size_t nbits, MetricType metric = METRIC_L2);
+    IndexPQ();
+    void train(idx_t n, const float* x) override;
+    void add(idx_t n, const float* x) override;
+    void search_device(idx_t n, const float* x, int ldx, idx_t k, float* distances,
+                       idx_t* labels, const SearchParameters* params,
+                       hipStream_t stream) const override;
+    // also counts indexPQ_stats (nq, ncode), as faiss/IndexPQ.cpp:170-172
+    void search(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels,
+                const SearchParameters* params = nullptr) const override;
+    void reset() override;
+    void reconstruct(idx_t key, float* recons) const override;
+    void reconstruct_n(idx_t i0, idx_t ni, float* recons) const override;
+    // faiss/IndexFlatCodes.cpp:53-73: sel is asked about row numbers
+    size_t remove_ids(const IDSelector& sel) override;
+    void sync_device() const override;
+    int device_code_stride() const { return (int)roundup(code_size, 4); }
+    // throws unless the search type (the params', else the index's) is ST_PQ
+    // and there is no selector
+    void check_search(const SearchParameters* params) const;
+    // what assigning the public fields does, plus the bookkeeping: centroids
+    // [M][ksub][dsub] (null: kept; is_trained becomes true), then the whole
+    // code array, n rows (null: kept); the next search uploads them
+    void set_content(const float* centroids, idx_t n, const uint8_t* codes);
+
+   protected:
+    mutable std::recursive_mutex mu_;
+    mutable StreamOrder order_;
+    mutable bool dirty_ = true;
+    mutable DeviceBuffer d_codes_, d_pq_, s_part_, s_tab_, s_dense_;
 };
 
 // ---------------------------------------------------------------- refine
@@ -1313,8 +1386,8 @@ Index* read_index(const char* fname, int io_flags = 0);
 void write_index_ondisk(const Index* idx, const char* fname, const char* lists_fname);
 Index* read_index(FILE* f, int io_flags = 0);
 
-// faiss/index_factory.h (subset: Flat, IVFn[_HNSWm],Flat|PQm[xb][np]|SQ8|SQfp16, HNSWm,
-// each optionally followed by ",RFlat" / ",Refine(Flat)")
+// faiss/index_factory.h (subset: Flat, PQm[xb], IVFn[_HNSWm],Flat|PQm[xb][np]|SQ8|SQfp16,
+// HNSWm, each optionally followed by ",RFlat" / ",Refine(Flat)")
 Index* index_factory(int d, const char* description, MetricType metric = METRIC_L2);
 
 // The reference's IndexIVF::search cuts a batch into min(omp threads, n)

@@ -233,6 +233,33 @@ FaissIndexFlat* faiss_IndexFlat_cast(FaissIndex* index);
 FaissIndexFlatIP* faiss_IndexFlatIP_cast(FaissIndex* index);
 FaissIndexFlatL2* faiss_IndexFlatL2_cast(FaissIndex* index);
 
+/* ---------------- IndexPQ (faiss/IndexPQ.h; the reference C API has no header
+ * for it, so the names follow its other classes) ---------------- */
+typedef struct FaissIndex_H FaissIndexPQ;
+int faiss_IndexPQ_new_with(FaissIndexPQ** p_index, idx_t d, size_t M, size_t nbits,
+                           FaissMetricType metric);
+void faiss_IndexPQ_free(FaissIndexPQ* obj);
+FaissIndexPQ* faiss_IndexPQ_cast(FaissIndex* index);
+/* M, nbits, code_size, search_type (IndexPQ::Search_type_t) */
+int faiss_amd_IndexPQ_info(const FaissIndexPQ* index, size_t* M, size_t* nbits, size_t* code_size,
+                           int* search_type);
+int faiss_amd_IndexPQ_set_search_type(FaissIndexPQ* index, int search_type);
+/* pointers to the host fields pq.centroids [M][ksub][dsub] and codes
+ * [ntotal][code_size] */
+void faiss_amd_IndexPQ_pq_centroids(FaissIndexPQ* index, float** p_centroids, size_t* p_size);
+void faiss_amd_IndexPQ_codes(FaissIndexPQ* index, uint8_t** p_codes, size_t* p_size);
+/* what assigning the reference's public fields does: the codebooks (null:
+ * kept; is_trained becomes true) and the whole code array (n rows; null: kept) */
+int faiss_amd_IndexPQ_set_content(FaissIndexPQ* index, const float* centroids, idx_t n,
+                                  const uint8_t* codes);
+/* SearchParametersPQ (faiss/IndexPQ.h:152-156); sel may be null */
+int faiss_amd_SearchParametersPQ_new(int search_type, int polysemous_ht,
+                                     FaissIDSelector* sel, FaissSearchParameters** p_sp);
+void faiss_amd_SearchParametersPQ_free(FaissSearchParameters* obj);
+/* the global indexPQ_stats */
+void faiss_amd_indexPQ_stats(size_t* nq, size_t* ncode);
+void faiss_amd_indexPQ_stats_reset(void);
+
 /* ---------------- IndexRefineFlat (c_api/IndexFlat_c.h:89-107) ----------------
  * Searches k * k_factor candidates in base_index (a fast, compressed index)
  * and re-ranks them with exact distances from a flat copy of the vectors. */
