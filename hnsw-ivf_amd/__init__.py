@@ -321,6 +321,44 @@ def _declare(L):
         "faiss_amd_indexPQ_stats": (None, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
         "faiss_amd_indexPQ_stats_reset": (None, []),
         "faiss_amd_SearchParametersPreTransform_free": (None, [_P]),
+        "faiss_IndexBinary_free": (None, [_P]),
+        "faiss_IndexBinary_d": (C.c_int, [_P]),
+        "faiss_IndexBinary_is_trained": (C.c_int, [_P]),
+        "faiss_IndexBinary_ntotal": (_I64, [_P]),
+        "faiss_IndexBinary_train": (C.c_int, [_P, _I64, _P]),
+        "faiss_IndexBinary_add": (C.c_int, [_P, _I64, _P]),
+        "faiss_IndexBinary_add_with_ids": (C.c_int, [_P, _I64, _P, _P]),
+        "faiss_IndexBinary_search": (C.c_int, [_P, _I64, _P, _I64, _P, _P]),
+        "faiss_IndexBinary_reset": (C.c_int, [_P]),
+        "faiss_IndexBinary_reconstruct": (C.c_int, [_P, _I64, _P]),
+        "faiss_IndexBinaryFlat_new": (C.c_int, [C.POINTER(_P), _I64]),
+        "faiss_IndexBinaryFlat_cast": (_P, [_P]),
+        "faiss_IndexBinaryIVF_new": (C.c_int, [C.POINTER(_P), _P, C.c_size_t, C.c_size_t]),
+        "faiss_IndexBinaryIVF_cast": (_P, [_P]),
+        "faiss_read_index_binary_fname": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
+        "faiss_write_index_binary_fname": (C.c_int, [_P, C.c_char_p]),
+        "faiss_index_binary_factory": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p]),
+        "faiss_amd_IndexBinary_class_name": (C.c_char_p, [_P]),
+        "faiss_amd_IndexBinary_search_with_params": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+        "faiss_amd_IndexBinary_search_device": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+        "faiss_amd_IndexBinary_remove_ids": (C.c_int, [_P, _P, C.POINTER(C.c_size_t)]),
+        "faiss_amd_IndexBinary_range_search": (C.c_int, [_P, _I64, _P, C.c_int]),
+        "faiss_amd_IndexBinary_use_heap": (C.c_int, [_P]),
+        "faiss_amd_IndexBinary_set_use_heap": (C.c_int, [_P, C.c_int]),
+        "faiss_amd_IndexBinary_set_is_trained": (C.c_int, [_P, C.c_int]),
+        "faiss_amd_IndexBinaryIVF_nlist": (C.c_size_t, [_P]),
+        "faiss_amd_IndexBinaryIVF_nprobe": (C.c_size_t, [_P]),
+        "faiss_amd_IndexBinaryIVF_set_nprobe": (C.c_int, [_P, C.c_size_t]),
+        "faiss_amd_IndexBinaryIVF_max_codes": (C.c_size_t, [_P]),
+        "faiss_amd_IndexBinaryIVF_set_max_codes": (C.c_int, [_P, C.c_size_t]),
+        "faiss_amd_IndexBinaryIVF_set_own_fields": (C.c_int, [_P, C.c_int]),
+        "faiss_amd_IndexBinaryIVF_set_per_invlist_search": (C.c_int, [_P, C.c_int]),
+        "faiss_amd_IndexBinaryIVF_quantizer": (_P, [_P]),
+        "faiss_amd_IndexBinaryIVF_set_direct_map_type": (C.c_int, [_P, C.c_int]),
+        "faiss_amd_IndexBinaryIVF_reconstruct_n": (C.c_int, [_P, _I64, _I64, _P]),
+        "faiss_amd_IndexBinaryIVF_search_preassigned": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _P,
+                                                                  C.c_int, _P]),
+        "faiss_amd_IndexBinaryIVF_merge_from": (C.c_int, [_P, _P, _I64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1029,6 +1067,187 @@ def indexPQ_stats(reset=False):
     nq, nc = C.c_size_t(), C.c_size_t()
     lib().faiss_amd_indexPQ_stats(C.byref(nq), C.byref(nc))
     return dict(nq=nq.value, ncode=nc.value)
+
+
+# ---------------------------------------------------------------- binary
+def _u8(x):
+    x = np.ascontiguousarray(x, dtype=np.uint8)
+    assert x.ndim == 2
+    return x
+
+
+class IndexBinary:
+    """Wraps a FaissIndexBinary* handle: vectors are uint8 rows of d / 8 bytes,
+    search returns (int32 D, int64 I), padded with (INT32_MAX, -1)."""
+
+    def __init__(self, handle, owner=None):
+        self.h = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+        self._owner = owner
+
+    def __del__(self):
+        try:
+            if self._owner is None and self.h and self.h.value and _lib is not None:
+                _lib.faiss_IndexBinary_free(self.h)
+                self.h = C.c_void_p(None)
+        except Exception:
+            pass
+
+    d = property(lambda self: lib().faiss_IndexBinary_d(self.h))
+    ntotal = property(lambda self: lib().faiss_IndexBinary_ntotal(self.h))
+    code_size = property(lambda self: self.d // 8)
+
+    @property
+    def is_trained(self):
+        return bool(lib().faiss_IndexBinary_is_trained(self.h))
+
+    @is_trained.setter
+    def is_trained(self, v):
+        lib().faiss_amd_IndexBinary_set_is_trained(self.h, int(bool(v)))
+
+    @property
+    def use_heap(self):
+        return bool(lib().faiss_amd_IndexBinary_use_heap(self.h))
+
+    @use_heap.setter
+    def use_heap(self, v):
+        _check(lib().faiss_amd_IndexBinary_set_use_heap(self.h, int(bool(v))))
+
+    def train(self, x):
+        x = _u8(x)
+        _check(lib().faiss_IndexBinary_train(self.h, x.shape[0], _ptr(x)))
+
+    def add(self, x):
+        x = _u8(x)
+        assert x.shape[1] == self.code_size
+        _check(lib().faiss_IndexBinary_add(self.h, x.shape[0], _ptr(x)))
+
+    def add_with_ids(self, x, ids):
+        x = _u8(x)
+        assert x.shape[1] == self.code_size
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        _check(lib().faiss_IndexBinary_add_with_ids(self.h, x.shape[0], _ptr(x), _ptr(ids)))
+
+    def search(self, x, k, params=None):
+        x = _u8(x)
+        assert x.shape[1] == self.code_size
+        n = x.shape[0]
+        D = np.empty((n, k), dtype=np.int32)
+        I = np.empty((n, k), dtype=np.int64)
+        _check(lib().faiss_amd_IndexBinary_search_with_params(
+            self.h, n, _ptr(x), k, params.h if params is not None else None, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_device(self, n, x_ptr, k, d_ptr, i_ptr, stream=None):
+        """Device pointers: query rows of ceil(d / 32) zero-padded dwords."""
+        _check(lib().faiss_amd_IndexBinary_search_device(self.h, n, x_ptr, k, d_ptr, i_ptr, stream))
+
+    def range_search(self, x, radius):
+        x = _u8(x)
+        _check(lib().faiss_amd_IndexBinary_range_search(self.h, x.shape[0], _ptr(x), int(radius)))
+
+    def reset(self):
+        _check(lib().faiss_IndexBinary_reset(self.h))
+
+    def remove_ids(self, sel):
+        n = C.c_size_t(0)
+        _check(lib().faiss_amd_IndexBinary_remove_ids(self.h, sel.h, C.byref(n)))
+        return n.value
+
+    def reconstruct(self, key):
+        out = np.empty(self.code_size, dtype=np.uint8)
+        _check(lib().faiss_IndexBinary_reconstruct(self.h, int(key), _ptr(out)))
+        return out
+
+
+class IndexBinaryFlat(IndexBinary):
+    """faiss.IndexBinaryFlat: exhaustive Hamming search on the GPU."""
+
+    def __init__(self, d=None, handle=None, owner=None):
+        if handle is None:
+            handle = C.c_void_p()
+            _check(lib().faiss_IndexBinaryFlat_new(C.byref(handle), d))
+        super().__init__(handle, owner)
+
+
+class IndexBinaryIVF(IndexBinary):
+    """faiss.IndexBinaryIVF over an IndexBinaryFlat quantizer."""
+
+    def __init__(self, quantizer=None, d=None, nlist=None, handle=None, owner=None):
+        if handle is None:
+            handle = C.c_void_p()
+            _check(lib().faiss_IndexBinaryIVF_new(C.byref(handle), quantizer.h, d, nlist))
+            self._quantizer = quantizer  # not owned by the index: kept alive here
+        super().__init__(handle, owner)
+
+    nlist = property(lambda self: lib().faiss_amd_IndexBinaryIVF_nlist(self.h))
+
+    @property
+    def quantizer(self):
+        return _wrap_binary(lib().faiss_amd_IndexBinaryIVF_quantizer(self.h), owner=self)
+
+    @property
+    def nprobe(self):
+        return lib().faiss_amd_IndexBinaryIVF_nprobe(self.h)
+
+    @nprobe.setter
+    def nprobe(self, v):
+        _check(lib().faiss_amd_IndexBinaryIVF_set_nprobe(self.h, int(v)))
+
+    @property
+    def max_codes(self):
+        return lib().faiss_amd_IndexBinaryIVF_max_codes(self.h)
+
+    @max_codes.setter
+    def max_codes(self, v):
+        _check(lib().faiss_amd_IndexBinaryIVF_set_max_codes(self.h, int(v)))
+
+    def set_per_invlist_search(self, v):
+        _check(lib().faiss_amd_IndexBinaryIVF_set_per_invlist_search(self.h, int(bool(v))))
+
+    def set_direct_map_type(self, t):
+        _check(lib().faiss_amd_IndexBinaryIVF_set_direct_map_type(self.h, int(t)))
+
+    def reconstruct_n(self, i0, ni):
+        out = np.empty((ni, self.code_size), dtype=np.uint8)
+        _check(lib().faiss_amd_IndexBinaryIVF_reconstruct_n(self.h, i0, ni, _ptr(out)))
+        return out
+
+    def search_preassigned(self, x, k, assign, store_pairs=False, params=None):
+        x = _u8(x)
+        assign = np.ascontiguousarray(assign, dtype=np.int64)
+        n = x.shape[0]
+        D = np.empty((n, k), dtype=np.int32)
+        I = np.empty((n, k), dtype=np.int64)
+        _check(lib().faiss_amd_IndexBinaryIVF_search_preassigned(
+            self.h, n, _ptr(x), k, _ptr(assign), _ptr(D), _ptr(I), int(store_pairs),
+            params.h if params is not None else None))
+        return D, I
+
+    def merge_from(self, other, add_id=0):
+        _check(lib().faiss_amd_IndexBinaryIVF_merge_from(self.h, other.h, add_id))
+
+
+def _wrap_binary(h, owner=None):
+    h = h if isinstance(h, C.c_void_p) else C.c_void_p(h)
+    name = lib().faiss_amd_IndexBinary_class_name(h).decode()
+    cls = {"IndexBinaryFlat": IndexBinaryFlat, "IndexBinaryIVF": IndexBinaryIVF}[name]
+    return cls(handle=h, owner=owner)
+
+
+def index_binary_factory(d, description):
+    p = C.c_void_p()
+    _check(lib().faiss_index_binary_factory(C.byref(p), d, description.encode()))
+    return _wrap_binary(p)
+
+
+def read_index_binary(fname, io_flags=0):
+    p = C.c_void_p()
+    _check(lib().faiss_read_index_binary_fname(str(fname).encode(), io_flags, C.byref(p)))
+    return _wrap_binary(p)
+
+
+def write_index_binary(index, fname):
+    _check(lib().faiss_write_index_binary_fname(index.h, str(fname).encode()))
 
 
 class IndexRefineFlat(Index):

@@ -1590,4 +1590,182 @@ int faiss_amd_float_rand_rows(float* out, int64_t n_rows, int d, int64_t seed, i
     C_CATCH
 }
 
+// ---------------- binary indexes (c_api/IndexBinary_c.h)
+#define BX(p) reinterpret_cast<IndexBinary*>(const_cast<FaissIndexBinary*>(p))
+#define BFX(p) reinterpret_cast<FaissIndexBinary*>(p)
+static IndexBinaryIVF* BIVF(const FaissIndexBinary* p) {
+    auto r = dynamic_cast<IndexBinaryIVF*>(BX(p));
+    FAISS_THROW_IF_NOT_MSG(r, "index is not an IndexBinaryIVF");
+    return r;
+}
+void faiss_IndexBinary_free(FaissIndexBinary* obj) { delete BX(obj); }
+int faiss_IndexBinary_d(const FaissIndexBinary* i) { return BX(i)->d; }
+int faiss_IndexBinary_is_trained(const FaissIndexBinary* i) { return BX(i)->is_trained ? 1 : 0; }
+idx_t faiss_IndexBinary_ntotal(const FaissIndexBinary* i) { return BX(i)->ntotal; }
+FaissMetricType faiss_IndexBinary_metric_type(const FaissIndexBinary* i) {
+    return (FaissMetricType)BX(i)->metric_type;
+}
+int faiss_IndexBinary_verbose(const FaissIndexBinary* i) { return BX(i)->verbose ? 1 : 0; }
+void faiss_IndexBinary_set_verbose(FaissIndexBinary* i, int v) { BX(i)->verbose = v != 0; }
+int faiss_IndexBinary_train(FaissIndexBinary* index, idx_t n, const uint8_t* x) {
+    C_TRY BX(index)->train(n, x);
+    C_CATCH
+}
+int faiss_IndexBinary_add(FaissIndexBinary* index, idx_t n, const uint8_t* x) {
+    C_TRY BX(index)->add(n, x);
+    C_CATCH
+}
+int faiss_IndexBinary_add_with_ids(FaissIndexBinary* index, idx_t n, const uint8_t* x,
+                                   const idx_t* xids) {
+    C_TRY BX(index)->add_with_ids(n, x, xids);
+    C_CATCH
+}
+int faiss_IndexBinary_search(const FaissIndexBinary* index, idx_t n, const uint8_t* x, idx_t k,
+                             int32_t* distances, idx_t* labels) {
+    C_TRY BX(index)->search(n, x, k, distances, labels, nullptr);
+    C_CATCH
+}
+int faiss_amd_IndexBinary_search_with_params(const FaissIndexBinary* index, idx_t n,
+                                             const uint8_t* x, idx_t k,
+                                             const FaissSearchParameters* params,
+                                             int32_t* distances, idx_t* labels) {
+    C_TRY BX(index)->search(n, x, k, distances, labels, resolve_params(params));
+    C_CATCH
+}
+int faiss_amd_IndexBinary_search_device(const FaissIndexBinary* index, idx_t n,
+                                        const uint32_t* x_dev, idx_t k, int32_t* d_dev,
+                                        idx_t* l_dev, void* stream) {
+    C_TRY const IndexBinary* ix = BX(index);
+    ensure_hip();
+    ix->sync_device();
+    ix->search_device(n, x_dev, k, d_dev, l_dev, nullptr,
+                      stream ? (hipStream_t)stream : ix->stream());
+    C_CATCH
+}
+int faiss_IndexBinary_reset(FaissIndexBinary* index) {
+    C_TRY BX(index)->reset();
+    C_CATCH
+}
+int faiss_IndexBinary_reconstruct(const FaissIndexBinary* index, idx_t key, uint8_t* recons) {
+    C_TRY BX(index)->reconstruct(key, recons);
+    C_CATCH
+}
+int faiss_amd_IndexBinary_remove_ids(FaissIndexBinary* index, const FaissIDSelector* sel,
+                                     size_t* n_removed) {
+    C_TRY const size_t r = BX(index)->remove_ids(*reinterpret_cast<const IDSelector*>(sel));
+    if (n_removed) *n_removed = r;
+    C_CATCH
+}
+int faiss_amd_IndexBinary_range_search(const FaissIndexBinary* index, idx_t n, const uint8_t* x,
+                                       int radius) {
+    C_TRY RangeSearchResult res((size_t)n);
+    BX(index)->range_search(n, x, radius, &res);
+    C_CATCH
+}
+int faiss_IndexBinaryFlat_new(FaissIndexBinaryFlat** p_index, idx_t d) {
+    C_TRY* p_index = BFX(static_cast<IndexBinary*>(new IndexBinaryFlat(d)));
+    C_CATCH
+}
+FaissIndexBinaryFlat* faiss_IndexBinaryFlat_cast(FaissIndexBinary* index) {
+    return dynamic_cast<IndexBinaryFlat*>(BX(index)) ? index : nullptr;
+}
+int faiss_IndexBinaryIVF_new(FaissIndexBinaryIVF** p_index, FaissIndexBinary* quantizer, size_t d,
+                             size_t nlist) {
+    C_TRY* p_index = BFX(static_cast<IndexBinary*>(new IndexBinaryIVF(BX(quantizer), d, nlist)));
+    C_CATCH
+}
+FaissIndexBinaryIVF* faiss_IndexBinaryIVF_cast(FaissIndexBinary* index) {
+    return dynamic_cast<IndexBinaryIVF*>(BX(index)) ? index : nullptr;
+}
+int faiss_read_index_binary_fname(const char* fname, int io_flags, FaissIndexBinary** p_out) {
+    C_TRY* p_out = BFX(read_index_binary(fname, io_flags));
+    C_CATCH
+}
+int faiss_write_index_binary_fname(const FaissIndexBinary* idx, const char* fname) {
+    C_TRY write_index_binary(BX(idx), fname);
+    C_CATCH
+}
+int faiss_index_binary_factory(FaissIndexBinary** p_index, int d, const char* description) {
+    C_TRY* p_index = BFX(index_binary_factory(d, description));
+    C_CATCH
+}
+const char* faiss_amd_IndexBinary_class_name(const FaissIndexBinary* index) {
+    return BX(index)->class_name();
+}
+int faiss_amd_IndexBinary_use_heap(const FaissIndexBinary* index) {
+    if (auto f = dynamic_cast<IndexBinaryFlat*>(BX(index))) return f->use_heap ? 1 : 0;
+    if (auto v = dynamic_cast<IndexBinaryIVF*>(BX(index))) return v->use_heap ? 1 : 0;
+    return -1;
+}
+int faiss_amd_IndexBinary_set_use_heap(FaissIndexBinary* index, int use_heap) {
+    C_TRY if (auto f = dynamic_cast<IndexBinaryFlat*>(BX(index))) f->use_heap = use_heap != 0;
+    else BIVF(index)->use_heap = use_heap != 0;
+    C_CATCH
+}
+int faiss_amd_IndexBinary_set_is_trained(FaissIndexBinary* index, int is_trained) {
+    BX(index)->is_trained = is_trained != 0;
+    return 0;
+}
+size_t faiss_amd_IndexBinaryIVF_nlist(const FaissIndexBinaryIVF* i) {
+    auto v = dynamic_cast<IndexBinaryIVF*>(BX(i));
+    return v ? v->nlist : 0;
+}
+size_t faiss_amd_IndexBinaryIVF_nprobe(const FaissIndexBinaryIVF* i) {
+    auto v = dynamic_cast<IndexBinaryIVF*>(BX(i));
+    return v ? v->nprobe : 0;
+}
+int faiss_amd_IndexBinaryIVF_set_nprobe(FaissIndexBinaryIVF* i, size_t nprobe) {
+    C_TRY BIVF(i)->nprobe = nprobe;
+    C_CATCH
+}
+size_t faiss_amd_IndexBinaryIVF_max_codes(const FaissIndexBinaryIVF* i) {
+    auto v = dynamic_cast<IndexBinaryIVF*>(BX(i));
+    return v ? v->max_codes : 0;
+}
+int faiss_amd_IndexBinaryIVF_set_max_codes(FaissIndexBinaryIVF* i, size_t max_codes) {
+    C_TRY BIVF(i)->max_codes = max_codes;
+    C_CATCH
+}
+int faiss_amd_IndexBinaryIVF_set_own_fields(FaissIndexBinaryIVF* i, int own_fields) {
+    C_TRY BIVF(i)->own_fields = own_fields != 0;
+    C_CATCH
+}
+int faiss_amd_IndexBinaryIVF_set_per_invlist_search(FaissIndexBinaryIVF* i, int v) {
+    C_TRY BIVF(i)->per_invlist_search = v != 0;
+    C_CATCH
+}
+FaissIndexBinary* faiss_amd_IndexBinaryIVF_quantizer(FaissIndexBinaryIVF* i) {
+    auto v = dynamic_cast<IndexBinaryIVF*>(BX(i));
+    return v ? BFX(v->quantizer) : nullptr;
+}
+int faiss_amd_IndexBinaryIVF_set_direct_map_type(FaissIndexBinaryIVF* i, int type) {
+    C_TRY FAISS_THROW_IF_NOT(type >= 0 && type <= 2);
+    BIVF(i)->set_direct_map_type((DirectMap::Type)type);
+    C_CATCH
+}
+int faiss_amd_IndexBinaryIVF_reconstruct_n(const FaissIndexBinaryIVF* i, idx_t i0, idx_t ni,
+                                           uint8_t* recons) {
+    C_TRY BIVF(i)->reconstruct_n(i0, ni, recons);
+    C_CATCH
+}
+int faiss_amd_IndexBinaryIVF_search_preassigned(const FaissIndexBinaryIVF* i, idx_t n,
+                                                const uint8_t* x, idx_t k, const idx_t* assign,
+                                                int32_t* distances, idx_t* labels,
+                                                int store_pairs,
+                                                const FaissSearchParameters* params) {
+    C_TRY auto sp = resolve_params(params);
+    auto ivfp = dynamic_cast<const SearchParametersIVF*>(sp);
+    FAISS_THROW_IF_NOT_MSG(!sp || ivfp, "IndexBinaryIVF: params type invalid");
+    BIVF(i)->search_preassigned(n, x, k, assign, nullptr, distances, labels, store_pairs != 0,
+                                ivfp);
+    C_CATCH
+}
+int faiss_amd_IndexBinaryIVF_merge_from(FaissIndexBinaryIVF* i, FaissIndexBinaryIVF* other,
+                                        idx_t add_id) {
+    C_TRY BIVF(i)->merge_from(*BIVF(other), add_id);
+    C_CATCH
+}
+#undef BX
+#undef BFX
+
 }  // extern "C"

@@ -848,6 +848,140 @@ Index* read_index(const char* fname, int io_flags) {
     return idx;
 }
 
+// ---------------------------------------------------------------- binary
+//   IBxF = binary header (d:i32, code_size:i32, ntotal:i64, is_trained:u8,
+//          metric:i32), xb:vec<u8>                 (index_write.cpp:874-883, 957-960)
+//   IBwF = binary header, nlist:size_t, nprobe:size_t, quantizer (binary
+//          index), direct map, inverted lists      (index_write.cpp:885-891, 964-967)
+namespace {
+void write_binary_impl(const IndexBinary* idx, Writer& w) {
+    auto header = [&](const IndexBinary* b) {
+        w.one<int32_t>(b->d);
+        w.one<int32_t>(b->code_size);
+        w.one<int64_t>(b->ntotal);
+        w.one<uint8_t>(b->is_trained ? 1 : 0);
+        w.one<int32_t>((int32_t)b->metric_type);
+    };
+    if (auto f = dynamic_cast<const IndexBinaryFlat*>(idx)) {
+        w.one(fourcc("IBxF"));
+        header(f);
+        w.vec(f->xb);
+    } else if (auto ivf = dynamic_cast<const IndexBinaryIVF*>(idx)) {
+        w.one(fourcc("IBwF"));
+        header(ivf);
+        w.one<size_t>(ivf->nlist);
+        w.one<size_t>(ivf->nprobe);
+        write_binary_impl(ivf->quantizer, w);
+        const DirectMap& dm = ivf->direct_map;
+        w.one<char>((char)dm.type);
+        w.vec(dm.array);
+        if (dm.type == DirectMap::Hashtable) {
+            std::vector<std::pair<idx_t, idx_t>> v(dm.hashtable.begin(), dm.hashtable.end());
+            std::sort(v.begin(), v.end());
+            w.vec(v);
+        }
+        write_invlists(ivf->invlists.get(), w);
+    } else {
+        FAISS_THROW_MSG("don't know how to serialize this type of index");
+    }
+}
+
+IndexBinary* read_binary_impl(Reader& r, int io_flags) {
+    const uint32_t h = r.one<uint32_t>();
+    auto header = [&](IndexBinary* b) {
+        b->d = r.one<int32_t>();
+        b->code_size = r.one<int32_t>();
+        b->ntotal = r.one<int64_t>();
+        b->is_trained = r.one<uint8_t>() != 0;
+        b->metric_type = (MetricType)r.one<int32_t>();
+        FAISS_THROW_IF_NOT(b->d > 0 && b->code_size * 8 == b->d && b->ntotal >= 0);
+    };
+    if (h == fourcc("IBxF")) {
+        auto f = std::make_unique<IndexBinaryFlat>();
+        header(f.get());
+        r.vec(f->xb);
+        FAISS_THROW_IF_NOT(f->xb.size() == (size_t)f->ntotal * f->code_size);
+        return f.release();
+    }
+    if (h == fourcc("IBwF")) {
+        auto ivf = std::make_unique<IndexBinaryIVF>();
+        header(ivf.get());
+        ivf->nlist = r.one<size_t>();
+        ivf->nprobe = r.one<size_t>();
+        ivf->quantizer = read_binary_impl(r, io_flags);
+        ivf->own_fields = true;
+        DirectMap& dmap = ivf->direct_map;
+        const char dm = r.one<char>();
+        FAISS_THROW_IF_NOT_FMT(dm == DirectMap::NoMap || dm == DirectMap::Array ||
+                                       dm == DirectMap::Hashtable,
+                               "direct map type %d is not known", (int)dm);
+        dmap.type = (DirectMap::Type)dm;
+        r.vec(dmap.array);
+        if (dmap.type == DirectMap::Hashtable) {
+            std::vector<std::pair<idx_t, idx_t>> v;
+            r.vec(v);
+            for (const auto& e : v) dmap.hashtable[e.first] = e.second;
+        }
+        ivf->invlists = std::make_unique<ArrayInvertedLists>(ivf->nlist, (size_t)ivf->code_size);
+        read_invlists(ivf->invlists.get(), r, ivf->nlist, (size_t)ivf->code_size, io_flags);
+        return ivf.release();
+    }
+    static const struct {
+        const char *tag, *kind;
+    } others[] = {{"IBFf", "IndexBinaryFromFloat"}, {"IBHf", "IndexBinaryHNSW"},
+                  {"IBMp", "IndexBinaryIDMap"},     {"IBM2", "IndexBinaryIDMap2"},
+                  {"IBHh", "IndexBinaryHash"},      {"IBHm", "IndexBinaryMultiHash"}};
+    for (auto& o : others)
+        FAISS_THROW_IF_NOT_FMT(h != fourcc(o.tag),
+                               "%s (\"%s\") is not served on this path (IndexBinaryFlat and "
+                               "IndexBinaryIVF over a flat quantizer are)",
+                               o.kind, o.tag);
+    FAISS_THROW_MSG("fourcc \"" + fourcc_str(h) + "\" not recognized as a binary index");
+}
+}  // namespace
+
+void write_index_binary(const IndexBinary* idx, const char* fname) {
+    AtomicFile f(fname);
+    Writer w{f.f};
+    write_binary_impl(idx, w);
+    f.commit();
+}
+IndexBinary* read_index_binary(const char* fname, int io_flags) {
+    FILE* f = fopen(fname, "rb");
+    FAISS_THROW_IF_NOT_MSG(f, std::string("could not open ") + fname + " for reading");
+    IndexBinary* idx = nullptr;
+    try {
+        Reader r{f, fname};
+        idx = read_binary_impl(r, io_flags);
+    } catch (...) {
+        fclose(f);
+        throw;
+    }
+    fclose(f);
+    return idx;
+}
+
+// faiss/index_factory.cpp:905-947: "BFlat" and "BIVF{nlist}"; the other
+// descriptions name classes this library does not have
+IndexBinary* index_binary_factory(int d, const char* description) {
+    const std::string s(description);
+    int a = 0, b = 0, used = 0;
+    if (s == "BFlat") return new IndexBinaryFlat(d);
+    if (sscanf(description, "BIVF%d_HNSW%d", &a, &b) == 2)
+        FAISS_THROW_MSG("index_binary_factory: " + s +
+                        ": an IndexBinaryHNSW quantizer is not supported (BIVF{nlist} is)");
+    if (sscanf(description, "BIVF%d%n", &a, &used) == 1 && (size_t)used == s.size() && a > 0) {
+        auto ivf = new IndexBinaryIVF(new IndexBinaryFlat(d), (size_t)d, (size_t)a);
+        ivf->own_fields = true;
+        return ivf;
+    }
+    if (s.rfind("BHNSW", 0) == 0)
+        FAISS_THROW_MSG("index_binary_factory: " + s + ": IndexBinaryHNSW is not supported");
+    if (s.rfind("BHash", 0) == 0)
+        FAISS_THROW_MSG("index_binary_factory: " + s + ": IndexBinaryHash is not supported");
+    FAISS_THROW_MSG("index_binary_factory: description " + s + " did not generate an index");
+}
+
 // ---------------------------------------------------------------- factory
 // faiss/index_factory.cpp:242-345 subset.
 namespace {

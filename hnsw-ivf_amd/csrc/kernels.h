@@ -345,6 +345,28 @@ void pq_flat_search(const PQFlatArgs& a, DeviceBuffer& s_part, DeviceBuffer& s_t
 // queries a work group holds tables for at this shape (*global_tables: they
 // do not fit the LDS and live in global scratch)
 int pq_flat_queries_per_group(const PQFlatArgs& a, bool* global_tables = nullptr);
+// ---------------- binary indexes (kernels_binary.hip) ----------------
+// Hamming k-NN over bit vectors of d bits stored as W = ceil(d / 32) zero-padded
+// dwords per row.  D / I [n][k]: int32 distances, pads (INT32_MAX, -1).
+// k <= kMaxKExact (k <= BIN_KSEL selects inside the scan), d <= BIN_MAX_D.
+// The scratch buffer grows on demand and is never shrunk.
+constexpr int BIN_KSEL = 32, BIN_MAX_D = 65536;
+// IndexBinaryFlat: the k smallest by (distance, row), sorted that way
+void binary_flat_search(const uint32_t* x, int64_t n, int d, const uint32_t* codes,
+                        int64_t ntotal, int k, DeviceBuffer& scratch, int32_t* D, int64_t* I,
+                        hipStream_t s);
+// coarse labels [n][np] -> assign [n][np]: invalid labels and, with max_codes,
+// the probes after the first list that brings the scanned rows to max_codes
+// become -1
+void binary_probes(const int64_t* coarse, int64_t n, int np, const uint32_t* list_len, int nlist,
+                   int64_t max_codes, int32_t* assign, hipStream_t s);
+// IndexBinaryIVF: one work group per (query, probe) over the arena rows of
+// list assign[q][p].  use_heap: the reference heap's result (labels = ids);
+// else the counting scan's (k smallest by (distance, arrival), in that order).
+void binary_ivf_scan(const uint32_t* x, int64_t n, int d, const uint32_t* codes,
+                     const int64_t* ids, const int64_t* list_off, const uint32_t* list_len,
+                     uint32_t max_list_len, const int32_t* assign, int np, int k, bool use_heap,
+                     DeviceBuffer& scratch, int32_t* D, int64_t* I, hipStream_t s);
 // exact top-k (reference heap semantics, label = col0 + column) of dense rows;
 // k > kMaxKExact runs with global scratch (required then)
 template <class OutIdx>

@@ -94,6 +94,14 @@ using faiss_amd::indexPQ_stats;
 using faiss_amd::IndexPQStats;
 using faiss_amd::SearchParametersPQ;
 
+// faiss/IndexBinary.h, IndexBinaryFlat.h, IndexBinaryIVF.h
+using faiss_amd::IndexBinary;
+using faiss_amd::IndexBinaryFlat;
+using faiss_amd::IndexBinaryIVF;
+using faiss_amd::index_binary_factory;
+using faiss_amd::read_index_binary;
+using faiss_amd::write_index_binary;
+
 // faiss/IndexRefine.h
 using faiss_amd::IndexRefine;
 using faiss_amd::IndexRefineFlat;

@@ -1390,6 +1390,137 @@ Index* read_index(FILE* f, int io_flags = 0);
 // HNSWm, each optionally followed by ",RFlat" / ",Refine(Flat)")
 Index* index_factory(int d, const char* description, MetricType metric = METRIC_L2);
 
+// ---------------------------------------------------------------- binary
+// faiss/IndexBinary.h:34-172: vectors of d bits (d % 8 == 0) as code_size =
+// d / 8 bytes, Hamming distances as int32.  A hierarchy of its own, as in the
+// reference.  HBM keeps the rows zero-padded to whole dwords and the searches
+// are kern::binary_flat_search / binary_ivf_scan (kernels_binary.hip); results
+// carry the reference's tie rules (DESIGN.md §4 "Binary indexes").
+struct IndexBinary {
+    int d = 0;
+    int code_size = 0;
+    idx_t ntotal = 0;
+    bool verbose = false;
+    bool is_trained = true;
+    MetricType metric_type = METRIC_L2;
+    int device = 0;
+
+    explicit IndexBinary(idx_t d = 0);
+    virtual ~IndexBinary();
+    virtual void train(idx_t n, const uint8_t* x);
+    virtual void add(idx_t n, const uint8_t* x) = 0;
+    virtual void add_with_ids(idx_t n, const uint8_t* x, const idx_t* xids);
+    // host pointers, synchronous
+    virtual void search(idx_t n, const uint8_t* x, idx_t k, int32_t* distances, idx_t* labels,
+                        const SearchParameters* params = nullptr) const;
+    // device pointers: query rows of device_words() dwords each, zero padded
+    virtual void search_device(idx_t n, const uint32_t* x, idx_t k, int32_t* distances,
+                               idx_t* labels, const SearchParameters* params,
+                               hipStream_t stream) const = 0;
+    virtual void range_search(idx_t n, const uint8_t* x, int radius, RangeSearchResult* result,
+                              const SearchParameters* params = nullptr) const;
+    virtual void reset() = 0;
+    virtual size_t remove_ids(const IDSelector& sel);
+    virtual void reconstruct(idx_t key, uint8_t* recons) const;
+    virtual void reconstruct_n(idx_t i0, idx_t ni, uint8_t* recons) const;
+    virtual void sync_device() const {}
+    virtual const char* class_name() const = 0;
+    int device_words() const { return (d + 31) / 32; }
+    hipStream_t stream() const;
+
+   protected:
+    mutable std::mutex host_mu_;
+    mutable DeviceBuffer h_x_, h_d_, h_i_;
+};
+
+// faiss/IndexBinaryFlat.h: exhaustive Hamming search.  Both use_heap modes
+// return the k smallest by (distance, id), as the reference's two scans do.
+struct IndexBinaryFlat : IndexBinary {
+    std::vector<uint8_t> xb;  // [ntotal][code_size]
+    bool use_heap = true;
+    size_t query_batch_size = 32;  // the reference's host blocking; no effect here
+
+    explicit IndexBinaryFlat(idx_t d = 0);
+    void add(idx_t n, const uint8_t* x) override;
+    void search(idx_t n, const uint8_t* x, idx_t k, int32_t* distances, idx_t* labels,
+                const SearchParameters* params = nullptr) const override;
+    void search_device(idx_t n, const uint32_t* x, idx_t k, int32_t* distances, idx_t* labels,
+                       const SearchParameters* params, hipStream_t stream) const override;
+    void reset() override;
+    size_t remove_ids(const IDSelector& sel) override;  // faiss/IndexBinaryFlat.cpp:95-112
+    void reconstruct(idx_t key, uint8_t* recons) const override;
+    void sync_device() const override;
+    const char* class_name() const override { return "IndexBinaryFlat"; }
+
+   protected:
+    mutable std::recursive_mutex mu_;
+    mutable StreamOrder order_;
+    mutable bool dirty_ = true;
+    mutable DeviceBuffer d_codes_, s_scan_;
+};
+
+// faiss/IndexBinaryIVF.h:35-240 over an IndexBinaryFlat of nlist binary
+// centroids.  Served: train, add, add_with_ids, reset, search,
+// search_preassigned, reconstruct / reconstruct_n through a direct map,
+// nprobe, max_codes, use_heap, SearchParametersIVF (nprobe, max_codes).
+// Thrown by name: other quantizers, store_pairs, per_invlist_search,
+// range_search, an IDSelector, merge_from.
+struct IndexBinaryIVF : IndexBinary {
+    std::unique_ptr<ArrayInvertedLists> invlists;
+    size_t nprobe = 1;
+    size_t max_codes = 0;
+    bool use_heap = true;
+    bool per_invlist_search = false;
+    DirectMap direct_map;
+    IndexBinary* quantizer = nullptr;
+    size_t nlist = 0;
+    bool own_fields = false;
+    int niter = 10;  // k-means iterations (faiss/IndexBinaryIVF.cpp:44 cp.niter)
+
+    IndexBinaryIVF(IndexBinary* quantizer, size_t d, size_t nlist);
+    IndexBinaryIVF();
+    ~IndexBinaryIVF() override;
+    // bits -> +-1 floats, this library's k-means, centroids thresholded at 0
+    // (faiss/IndexBinaryIVF.cpp:259-298); the centroids are not parity-checked
+    void train(idx_t n, const uint8_t* x) override;
+    void add(idx_t n, const uint8_t* x) override;
+    void add_with_ids(idx_t n, const uint8_t* x, const idx_t* xids) override;
+    void search(idx_t n, const uint8_t* x, idx_t k, int32_t* distances, idx_t* labels,
+                const SearchParameters* params = nullptr) const override;
+    void search_device(idx_t n, const uint32_t* x, idx_t k, int32_t* distances, idx_t* labels,
+                       const SearchParameters* params, hipStream_t stream) const override;
+    // assign [n][min(nlist, nprobe)] host list numbers (-1: none); the centroid
+    // distances are not read
+    void search_preassigned(idx_t n, const uint8_t* x, idx_t k, const idx_t* assign,
+                            const int32_t* centroid_dis, int32_t* distances, idx_t* labels,
+                            bool store_pairs, const SearchParametersIVF* params = nullptr) const;
+    void reset() override;
+    void reconstruct(idx_t key, uint8_t* recons) const override;
+    void reconstruct_n(idx_t i0, idx_t ni, uint8_t* recons) const override;
+    void merge_from(IndexBinaryIVF& other, idx_t add_id);
+    void set_direct_map_type(DirectMap::Type type);
+    void sync_device() const override;
+    const char* class_name() const override { return "IndexBinaryIVF"; }
+
+   protected:
+    void check_quantizer() const;
+    // the scan after the probes are known: coarse [n][np] int64 labels (device)
+    void scan_device(idx_t n, const uint32_t* x, idx_t k, const idx_t* coarse, int np,
+                     size_t max_codes, int32_t* distances, idx_t* labels, hipStream_t s) const;
+    mutable std::recursive_mutex mu_;
+    mutable StreamOrder order_;
+    mutable bool dirty_ = true;
+    mutable uint32_t max_list_len_ = 0;
+    mutable DeviceBuffer d_codes_, d_ids_, d_list_off_, d_list_len_, s_scan_, s_coarse_d_,
+            s_coarse_i_, s_assign_;
+};
+
+// faiss/index_io.h:49-74 (IBxF, IBwF records)
+void write_index_binary(const IndexBinary* idx, const char* fname);
+IndexBinary* read_index_binary(const char* fname, int io_flags = 0);
+// faiss/index_factory.h:24: "BFlat" and "BIVF{nlist}"
+IndexBinary* index_binary_factory(int d, const char* description);
+
 // The reference's IndexIVF::search cuts a batch into min(omp threads, n)
 // slices and quantizes each with the form its size selects (the direct
 // fvec_L2sqr form below distance_compute_blas_threshold = 20 queries, else

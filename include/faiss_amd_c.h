@@ -1002,6 +1002,82 @@ int faiss_amd_float_rand(float* x, size_t n, int64_t seed);
 int faiss_amd_float_rand_rows(float* out, int64_t n_rows, int d, int64_t seed, int64_t row0,
                               int64_t step, int64_t nout);
 
+/* ---------------- binary indexes (c_api/IndexBinary_c.h:25-164) ----------------
+ * Vectors of d bits as d / 8 bytes, Hamming distances as int32; results pad
+ * with (INT32_MAX, -1).  IndexBinaryFlat and IndexBinaryIVF over a flat
+ * quantizer; the constructors, casts, file functions and factory follow the
+ * reference's names for the float classes. */
+typedef struct FaissIndexBinary_H FaissIndexBinary;
+typedef struct FaissIndexBinary_H FaissIndexBinaryFlat;
+typedef struct FaissIndexBinary_H FaissIndexBinaryIVF;
+void faiss_IndexBinary_free(FaissIndexBinary* obj);
+int faiss_IndexBinary_d(const FaissIndexBinary*);
+int faiss_IndexBinary_is_trained(const FaissIndexBinary*);
+idx_t faiss_IndexBinary_ntotal(const FaissIndexBinary*);
+FaissMetricType faiss_IndexBinary_metric_type(const FaissIndexBinary*);
+int faiss_IndexBinary_verbose(const FaissIndexBinary*);
+void faiss_IndexBinary_set_verbose(FaissIndexBinary*, int);
+int faiss_IndexBinary_train(FaissIndexBinary* index, idx_t n, const uint8_t* x);
+int faiss_IndexBinary_add(FaissIndexBinary* index, idx_t n, const uint8_t* x);
+int faiss_IndexBinary_add_with_ids(FaissIndexBinary* index, idx_t n, const uint8_t* x,
+                                   const idx_t* xids);
+int faiss_IndexBinary_search(const FaissIndexBinary* index, idx_t n, const uint8_t* x, idx_t k,
+                             int32_t* distances, idx_t* labels);
+int faiss_IndexBinary_reset(FaissIndexBinary* index);
+int faiss_IndexBinary_reconstruct(const FaissIndexBinary* index, idx_t key, uint8_t* recons);
+int faiss_IndexBinaryFlat_new(FaissIndexBinaryFlat** p_index, idx_t d);
+FaissIndexBinaryFlat* faiss_IndexBinaryFlat_cast(FaissIndexBinary* index);
+/* the quantizer is not owned unless faiss_amd_IndexBinaryIVF_set_own_fields */
+int faiss_IndexBinaryIVF_new(FaissIndexBinaryIVF** p_index, FaissIndexBinary* quantizer, size_t d,
+                             size_t nlist);
+FaissIndexBinaryIVF* faiss_IndexBinaryIVF_cast(FaissIndexBinary* index);
+int faiss_read_index_binary_fname(const char* fname, int io_flags, FaissIndexBinary** p_out);
+int faiss_write_index_binary_fname(const FaissIndexBinary* idx, const char* fname);
+int faiss_index_binary_factory(FaissIndexBinary** p_index, int d, const char* description);
+/* extensions.  class_name: "IndexBinaryFlat" / "IndexBinaryIVF" */
+const char* faiss_amd_IndexBinary_class_name(const FaissIndexBinary* index);
+/* params: NULL or a FaissSearchParametersIVF (nprobe, max_codes) */
+int faiss_amd_IndexBinary_search_with_params(const FaissIndexBinary* index, idx_t n,
+                                             const uint8_t* x, idx_t k,
+                                             const FaissSearchParameters* params,
+                                             int32_t* distances, idx_t* labels);
+/* device pointers: query rows of ceil(d / 32) dwords each, zero padded;
+ * stream: a hipStream_t or NULL (the index's own) */
+int faiss_amd_IndexBinary_search_device(const FaissIndexBinary* index, idx_t n,
+                                        const uint32_t* x_dev, idx_t k, int32_t* d_dev,
+                                        idx_t* l_dev, void* stream);
+int faiss_amd_IndexBinary_remove_ids(FaissIndexBinary* index, const FaissIDSelector* sel,
+                                     size_t* n_removed);
+/* int radius; out of scope on this path: always an error naming the class */
+int faiss_amd_IndexBinary_range_search(const FaissIndexBinary* index, idx_t n, const uint8_t* x,
+                                       int radius);
+/* use_heap of either class; nprobe, max_codes, own_fields, per_invlist_search,
+ * the quantizer (borrowed) and nlist of an IndexBinaryIVF */
+int faiss_amd_IndexBinary_use_heap(const FaissIndexBinary* index);
+int faiss_amd_IndexBinary_set_use_heap(FaissIndexBinary* index, int use_heap);
+size_t faiss_amd_IndexBinaryIVF_nlist(const FaissIndexBinaryIVF* index);
+size_t faiss_amd_IndexBinaryIVF_nprobe(const FaissIndexBinaryIVF* index);
+int faiss_amd_IndexBinaryIVF_set_nprobe(FaissIndexBinaryIVF* index, size_t nprobe);
+size_t faiss_amd_IndexBinaryIVF_max_codes(const FaissIndexBinaryIVF* index);
+int faiss_amd_IndexBinaryIVF_set_max_codes(FaissIndexBinaryIVF* index, size_t max_codes);
+int faiss_amd_IndexBinaryIVF_set_own_fields(FaissIndexBinaryIVF* index, int own_fields);
+int faiss_amd_IndexBinaryIVF_set_per_invlist_search(FaissIndexBinaryIVF* index, int v);
+FaissIndexBinary* faiss_amd_IndexBinaryIVF_quantizer(FaissIndexBinaryIVF* index);
+/* is_trained of an index whose quantizer was filled by hand */
+int faiss_amd_IndexBinary_set_is_trained(FaissIndexBinary* index, int is_trained);
+/* DirectMap::Type: 0 none, 1 array, 2 hashtable */
+int faiss_amd_IndexBinaryIVF_set_direct_map_type(FaissIndexBinaryIVF* index, int type);
+int faiss_amd_IndexBinaryIVF_reconstruct_n(const FaissIndexBinaryIVF* index, idx_t i0, idx_t ni,
+                                           uint8_t* recons);
+/* assign [n][min(nlist, nprobe)] list numbers (-1: none) */
+int faiss_amd_IndexBinaryIVF_search_preassigned(const FaissIndexBinaryIVF* index, idx_t n,
+                                                const uint8_t* x, idx_t k, const idx_t* assign,
+                                                int32_t* distances, idx_t* labels,
+                                                int store_pairs,
+                                                const FaissSearchParameters* params);
+int faiss_amd_IndexBinaryIVF_merge_from(FaissIndexBinaryIVF* index, FaissIndexBinaryIVF* other,
+                                        idx_t add_id);
+
 #ifdef __cplusplus
 }
 #endif
