@@ -23,6 +23,16 @@ LIB_PATH = os.environ.get("FAISS_AMD_LIB") or os.path.join(_HERE, "lib", "libfai
 
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
+# IndexFlat only (reference faiss/MetricType.h:22-44)
+METRIC_L1 = 2
+METRIC_Linf = 3
+METRIC_Lp = 4
+METRIC_Canberra = 20
+METRIC_BrayCurtis = 21
+METRIC_JensenShannon = 22
+METRIC_Jaccard = 23
+METRIC_NaNEuclidean = 24
+METRIC_ABS_INNER_PRODUCT = 25
 IO_FLAG_ONDISK_SAME_DIR = 4  # reference faiss/index_io.h:51
 IO_FLAG_SKIP_IVF_DATA = 8  # :53
 IO_FLAG_MMAP = 8 | 0x646F0000  # :64 — lists mapped from the file, streamed to HBM
@@ -122,6 +132,8 @@ def _declare(L):
         "faiss_Index_is_trained": (C.c_int, [_P]),
         "faiss_Index_ntotal": (_I64, [_P]),
         "faiss_Index_metric_type": (C.c_int, [_P]),
+        "faiss_amd_Index_metric_arg": (C.c_float, [_P]),
+        "faiss_amd_Index_set_metric_arg": (None, [_P, C.c_float]),
         "faiss_Index_verbose": (C.c_int, [_P]),
         "faiss_Index_set_verbose": (None, [_P, C.c_int]),
         "faiss_Index_train": (C.c_int, [_P, _I64, _P]),
@@ -430,6 +442,15 @@ class Index:
     @property
     def metric_type(self):
         return lib().faiss_Index_metric_type(self.h)
+
+    @property
+    def metric_arg(self):
+        """The exponent of METRIC_Lp."""
+        return lib().faiss_amd_Index_metric_arg(self.h)
+
+    @metric_arg.setter
+    def metric_arg(self, v):
+        lib().faiss_amd_Index_set_metric_arg(self.h, float(v))
 
     @property
     def verbose(self):

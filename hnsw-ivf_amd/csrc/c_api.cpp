@@ -105,6 +105,8 @@ idx_t faiss_Index_ntotal(const FaissIndex* i) { return IX(i)->ntotal; }
 FaissMetricType faiss_Index_metric_type(const FaissIndex* i) {
     return (FaissMetricType)IX(i)->metric_type;
 }
+float faiss_amd_Index_metric_arg(const FaissIndex* i) { return IX(i)->metric_arg; }
+void faiss_amd_Index_set_metric_arg(FaissIndex* i, float v) { IX(i)->metric_arg = v; }
 int faiss_Index_verbose(const FaissIndex* i) { return IX(i)->verbose ? 1 : 0; }
 void faiss_Index_set_verbose(FaissIndex* i, int v) { IX(i)->verbose = v != 0; }
 

@@ -23,7 +23,29 @@ namespace faiss_amd {
 
 using idx_t = int64_t;
 
-enum MetricType { METRIC_INNER_PRODUCT = 0, METRIC_L2 = 1 };
+// faiss/MetricType.h:22-44.  IndexFlat serves all of them; every other index
+// L2 and inner product only.
+enum MetricType {
+    METRIC_INNER_PRODUCT = 0,
+    METRIC_L2 = 1,
+    METRIC_L1,
+    METRIC_Linf,
+    METRIC_Lp,  // sum |x - y|^metric_arg
+    METRIC_Canberra = 20,
+    METRIC_BrayCurtis,
+    METRIC_JensenShannon,
+    METRIC_Jaccard,  // a similarity: larger is closer
+    METRIC_NaNEuclidean,
+    METRIC_ABS_INNER_PRODUCT,
+};
+// faiss/MetricType.h:49-52
+constexpr bool is_similarity_metric(MetricType m) {
+    return m == METRIC_INNER_PRODUCT || m == METRIC_Jaccard;
+}
+// the metrics every index serves
+constexpr bool is_basic_metric(MetricType m) {
+    return m == METRIC_INNER_PRODUCT || m == METRIC_L2;
+}
 
 class FaissException : public std::exception {
    public:
@@ -76,6 +98,12 @@ class FaissException : public std::exception {
                             hipGetErrorString(__e), #expr);                        \
         }                                                                          \
     } while (0)
+
+// every index but IndexFlat serves L2 and inner product only
+#define FAISS_AMD_REQUIRE_BASIC_METRIC(M, WHAT)                                              \
+    FAISS_THROW_IF_NOT_FMT(::faiss_amd::is_basic_metric(M),                                  \
+                           "%s serves METRIC_L2 and METRIC_INNER_PRODUCT only, not metric %d", \
+                           WHAT, (int)(M))
 
 // Launch check: surfaces launch-configuration errors immediately.
 #define HIP_LAUNCH_CHECK() HIP_CHECK(hipGetLastError())

@@ -249,6 +249,13 @@ void IndexFlat::sync_device() const {
     hipStream_t s = stream();
     const int l = ld();
     d_xb_.reserve(sizeof(float) * std::max<idx_t>(ntotal, 1) * l);
+    if (!is_basic_metric(metric_type)) {
+        // metric_distances reads the rows alone: no norms, no bf16 images
+        if (ntotal > 0) upload_rows(d_xb_.as<float>(), l, xb.data(), (int)d, ntotal, s);
+        HIP_CHECK(hipStreamSynchronize(s));
+        dirty_ = false;
+        return;
+    }
     d_norms_.reserve(sizeof(float) * std::max<idx_t>(ntotal, 1));
     if (ntotal > 0) {
         upload_rows(d_xb_.as<float>(), l, xb.data(), (int)d, ntotal, s);
@@ -293,6 +300,10 @@ template <class OutIdx>
 bool IndexFlat::knn_device(idx_t n, const float* x, int ldx, int k, float* distances,
                            OutIdx* labels, hipStream_t s, void* qimg_out, idx_t batch_n) const {
     FAISS_THROW_IF_NOT_FMT(k >= 1, "k = %d must be >= 1", k);
+    // (every coarse-quantizer entry point comes through here)
+    FAISS_THROW_IF_NOT_FMT(is_basic_metric(metric_type),
+                           "an IndexFlat of metric %d cannot be used as a coarse quantizer",
+                           (int)metric_type);
     sync_device();
     std::lock_guard<std::recursive_mutex> g(mu_);
     order_.enter(s);
@@ -448,10 +459,50 @@ bool IndexFlat::knn_impl(idx_t n, const float* x, int ldx, int k, float* distanc
     return false;
 }
 
+// faiss/IndexFlat.cpp:55-67 -> knn_extra_metrics (faiss/utils/extra_distances.cpp:
+// 55-96): one form whatever the batch size.  Whole distance rows from the VALU
+// tile (kernels_flat_metrics.hip), queries in chunks of the 256 MiB tile
+// budget, then the exact select with the reference heap's arrival-order tie
+// rule: CMin (keep the largest) for the similarity Jaccard, CMax otherwise.
+void IndexFlat::search_extra_metric(idx_t n, const float* x, int ldx, idx_t k, float* distances,
+                                    idx_t* labels, hipStream_t s) const {
+    FAISS_THROW_IF_NOT_FMT(k >= 1, "k = %lld must be >= 1", (long long)k);
+    if (n <= 0) return;
+    sync_device();
+    std::lock_guard<std::recursive_mutex> g(mu_);
+    const int keep_min = !is_similarity_metric(metric_type);
+    const idx_t ny = std::max<idx_t>(ntotal, 1);
+    const idx_t qc = std::max<idx_t>(1, std::min<idx_t>(n, ((idx_t)1 << 26) / ny));  // floats
+    order_.enter(s);
+    try {
+        s_tile_.reserve(sizeof(float) * qc * ny);
+        ScopedKernelTimer tm(&ktimes, "flat_metric_distance+select_exact", 0.0, s);
+        for (idx_t q0 = 0; q0 < n; q0 += qc) {
+            const idx_t nq = std::min(qc, n - q0);
+            // (an unknown metric throws "Invalid metric" here, rows or not)
+            kern::metric_distances(x + q0 * ldx, nq, ldx, d_xb_.as<float>(), ntotal, ld(), d,
+                                   (int)metric_type, metric_arg, s_tile_.as<float>(), ntotal, s);
+            kern::select_rows_exact<idx_t>(s_tile_.as<float>(), nq, ntotal, ntotal, (int)k,
+                                           keep_min, 0, distances + q0 * k, labels + q0 * k, k, s,
+                                           &s_sel_);
+        }
+    } catch (...) {
+        order_.leave(s);
+        throw;
+    }
+    order_.leave(s);
+}
+
 void IndexFlat::search_device(idx_t n, const float* x, int ldx, idx_t k, float* distances,
                               idx_t* labels, const SearchParameters* params,
                               hipStream_t s) const {
     DeviceGuard g(device);
+    if (!is_basic_metric(metric_type)) {
+        FAISS_THROW_IF_NOT_MSG(!(params && params->sel),
+                               "a selector is not served with this metric");  // IndexFlat.cpp:56
+        search_extra_metric(n, x, ldx, k, distances, labels, s);
+        return;
+    }
     if (params && params->sel) {
         search_selected(n, x, ldx, k, distances, labels, params->sel, s);
         return;
@@ -550,6 +601,7 @@ void IndexFlat::range_search(idx_t n, const float* x, float radius, RangeSearchR
     result->lims.assign((size_t)n + 1, 0);
     result->labels.clear();
     result->distances.clear();
+    if (!is_basic_metric(metric_type)) FAISS_THROW_MSG("metric type not supported");  // :87-89
     if (n == 0 || ntotal == 0) return;
     DeviceGuard dg(device);
     sync_device();

@@ -283,6 +283,7 @@ int HNSW::random_level(std::mt19937& rng) const {
 // ---------------------------------------------------------------- IndexHNSW
 IndexHNSW::IndexHNSW(IndexFlat* st, int M)
         : Index(st ? st->d : 0, st ? st->metric_type : METRIC_L2), hnsw(M), storage(st) {
+    FAISS_AMD_REQUIRE_BASIC_METRIC(metric_type, "IndexHNSW");
     is_trained = true;
     if (st) device = st->device;
 }
@@ -294,8 +295,12 @@ IndexHNSW::~IndexHNSW() {
     if (h_fcnt_) (void)hipHostFree(h_fcnt_);
     if (own_fields) delete storage;
 }
+static IndexFlat* hnsw_flat_storage(int d, MetricType metric) {
+    FAISS_AMD_REQUIRE_BASIC_METRIC(metric, "IndexHNSWFlat");
+    return new IndexFlat(d, metric);
+}
 IndexHNSWFlat::IndexHNSWFlat(int d_, int M, MetricType metric)
-        : IndexHNSW(new IndexFlat(d_, metric), M) {
+        : IndexHNSW(hnsw_flat_storage(d_, metric), M) {
     own_fields = true;
 }
 

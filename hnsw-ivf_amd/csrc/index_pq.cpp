@@ -45,6 +45,7 @@ const char* search_type_name(int t) {
 
 IndexPQ::IndexPQ(int d_, size_t M, size_t nbits, MetricType metric)
         : Index(d_, metric), pq((size_t)d_, M, checked_nbits(nbits)) {
+    FAISS_AMD_REQUIRE_BASIC_METRIC(metric, "IndexPQ");
     code_size = (M * nbits + 7) / 8;
     is_trained = false;
 }

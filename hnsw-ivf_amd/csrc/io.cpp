@@ -4,7 +4,8 @@
 // Format (reference faiss/impl/index_write.cpp, faiss/impl/index_read.cpp):
 //   header  = d:i32 ntotal:i64 dummy:i64 dummy:i64 is_trained:u8 metric:i32
 //             [metric_arg:f32 if metric > 1]                 (write :79-90)
-//   IxF2/IxFI = header, size_t n4, n4*4 bytes of floats       (:396-403)
+//   IxF2/IxFI/IxFl = header, size_t n4, n4*4 bytes of floats  (:396-403; IxFl:
+//             a metric other than L2 / inner product)
 //   IVF hdr = header, nlist:size_t, nprobe:size_t, nested quantizer,
 //             direct map (char type, vector<idx_t> array, and for a
 //             Hashtable vector<(idx_t id, idx_t entry)>)        (:367-389)
@@ -196,7 +197,8 @@ struct Header {
     int32_t metric;
     float metric_arg = 0;
 };
-Header read_header(Reader& r) {
+// any_metric: IndexFlat, which serves every metric of the reference
+Header read_header(Reader& r, bool any_metric = false) {
     Header h;
     h.d = r.one<int32_t>();
     h.ntotal = r.one<int64_t>();
@@ -205,7 +207,7 @@ Header read_header(Reader& r) {
     h.is_trained = r.one<uint8_t>() != 0;
     h.metric = r.one<int32_t>();
     if (h.metric > 1) h.metric_arg = r.one<float>();
-    FAISS_THROW_IF_NOT_MSG(h.metric == METRIC_L2 || h.metric == METRIC_INNER_PRODUCT,
+    FAISS_THROW_IF_NOT_MSG(any_metric || is_basic_metric((MetricType)h.metric),
                            "only L2 / inner-product indexes are supported");
     return h;
 }
@@ -540,7 +542,10 @@ void write_index_impl(const Index* idx, Writer& w) {
     if (idx == nullptr) {
         w.one(fourcc("null"));
     } else if (auto f = dynamic_cast<const IndexFlat*>(idx)) {
-        w.one(fourcc(f->metric_type == METRIC_INNER_PRODUCT ? "IxFI" : "IxF2"));
+        // faiss/impl/index_write.cpp:396-403
+        w.one(fourcc(f->metric_type == METRIC_INNER_PRODUCT ? "IxFI"
+                     : f->metric_type == METRIC_L2          ? "IxF2"
+                                                            : "IxFl"));
         write_header(f, w);
         size_t n4 = f->xb.size();  // number of 4-byte words
         w.one(n4);
@@ -620,8 +625,9 @@ void write_index_impl(const Index* idx, Writer& w) {
 Index* read_index_impl(Reader& r, int io_flags) {
     uint32_t h = r.one<uint32_t>();
     if (h == fourcc("null")) return nullptr;
-    if (h == fourcc("IxF2") || h == fourcc("IxFI")) {
-        Header hd = read_header(r);
+    if (h == fourcc("IxF2") || h == fourcc("IxFI") || h == fourcc("IxFl")) {
+        // the metric is the header's, whatever the tag (faiss/impl/index_read.cpp:537-551)
+        Header hd = read_header(r, true);
         auto f = new IndexFlat(hd.d, (MetricType)hd.metric);
         apply_header(f, hd);
         size_t n4 = r.one<size_t>();
@@ -650,6 +656,8 @@ Index* read_index_impl(Reader& r, int io_flags) {
         Index* st = read_index_impl(r, io_flags);
         auto stf = dynamic_cast<IndexFlat*>(st);
         FAISS_THROW_IF_NOT_MSG(stf, "IHNf storage must be a flat index");
+        FAISS_THROW_IF_NOT_MSG(is_basic_metric(stf->metric_type),
+                               "only L2 / inner-product indexes are supported");
         ix->storage = stf;
         ix->own_fields = true;
         ix->device = stf->device;
@@ -759,6 +767,8 @@ Index* read_index_impl(Reader& r, int io_flags) {
                                std::string("IxRF: a refine index of type ") +
                                        index_type_name(refine.get()) +
                                        " is not served (IndexFlat only)");
+        FAISS_THROW_IF_NOT_MSG(is_basic_metric(refine->metric_type),
+                               "only L2 / inner-product indexes are supported");
         auto rf = std::make_unique<IndexRefineFlat>();
         apply_header(rf.get(), hd);
         rf->device = base->device;
@@ -1092,6 +1102,7 @@ Index* factory_plain(int d, const std::string& s_in, MetricType metric) {
         return std::stol(s.substr(st, pos - st));
     };
     if (s == "Flat") return new IndexFlat(d, metric);
+    FAISS_AMD_REQUIRE_BASIC_METRIC(metric, s.c_str());
     if (s.rfind("HNSW", 0) == 0) {
         size_t pos = 4;
         int M = s.size() > 4 ? (int)parse_int(pos) : 32;

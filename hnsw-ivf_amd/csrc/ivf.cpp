@@ -81,6 +81,7 @@ IndexIVF::IndexIVF(Index* q, size_t d_, size_t nl, size_t cs, MetricType metric)
         : Index(d_, metric), quantizer(q), nlist(nl), code_size(cs) {
     FAISS_THROW_IF_NOT(q != nullptr);
     FAISS_THROW_IF_NOT((size_t)q->d == d_);
+    FAISS_AMD_REQUIRE_BASIC_METRIC(metric, "IndexIVF");
     is_trained = q->is_trained && (size_t)q->ntotal == nlist;
     invlists = std::make_unique<ArrayInvertedLists>(nlist, code_size);
     device = q->device;
@@ -492,6 +493,10 @@ void IndexIVF::search_device(idx_t n, const float* x, int ldx, idx_t k, float* d
     const char* genv = getenv("FAISS_AMD_GRAPH");
     std::lock_guard<std::recursive_mutex> g(mu_);
     const auto* qflat = dynamic_cast<const IndexFlat*>(quantizer);
+    // (refused here, before a search graph is being captured)
+    FAISS_THROW_IF_NOT_FMT(!qflat || is_basic_metric(qflat->metric_type),
+                           "an IndexFlat of metric %d cannot be used as a coarse quantizer",
+                           (int)qflat->metric_type);
     // (FAISS_AMD_IVF_STATS: the debug counters synchronise inside the scan)
     const bool eligible = !(genv && !strcmp(genv, "0")) && params_in == nullptr && !qdone_ &&
                           !getenv("FAISS_AMD_IVF_STATS") && qflat != nullptr && get_search_slices() <= 1 && n > 0 && !dirty_;

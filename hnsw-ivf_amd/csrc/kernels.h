@@ -42,6 +42,13 @@ void pairwise_distances(const float* x, int64_t nx, int ldx, const float* xn,
 void direct_distances(const float* x, int64_t nx, int ldx, const float* y, int64_t ny, int ldy,
                       int d, int metric_l2, float* D, int64_t ldD, hipStream_t s);
 
+// IndexFlat's other metrics (kernels_flat_metrics.hip): D[i][j] = dist(x_i, y_j)
+// for METRIC_L1 .. METRIC_ABS_INNER_PRODUCT in the reference's evaluation order
+// (faiss/utils/extra_distances-inl.h) on a 64 x 64 VALU tile.  ldx, ldy
+// multiples of 4 and >= d.  Any other metric: "Invalid metric".
+void metric_distances(const float* x, int64_t nx, int ldx, const float* y, int64_t ny, int ldy,
+                      int d, int metric, float metric_arg, float* D, int64_t ldD, hipStream_t s);
+
 // Coarse top-k on bf16x3 MFMA + certified exact re-rank (kernels_coarse.hip);
 // identical results to pairwise_distances + select_rows for blocks of >= 20
 // queries.  plan.ok == false: not eligible (fall back to the f32 tile path).

@@ -38,6 +38,7 @@ const IndexRefineSearchParameters* refine_params(const SearchParameters* params_
 IndexRefine::IndexRefine(Index* base, Index* refine)
         : Index(base->d, base->metric_type), base_index(base), refine_index(refine) {
     // faiss/IndexRefine.cpp:21-34
+    FAISS_AMD_REQUIRE_BASIC_METRIC(base->metric_type, "IndexRefine");
     device = base->device;
     if (refine != nullptr) {
         FAISS_THROW_IF_NOT_FMT(dynamic_cast<const IndexFlat*>(refine),

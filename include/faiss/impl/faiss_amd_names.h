@@ -24,6 +24,16 @@ using faiss_amd::idx_t;
 using faiss_amd::MetricType;
 using faiss_amd::METRIC_INNER_PRODUCT;
 using faiss_amd::METRIC_L2;
+using faiss_amd::METRIC_L1;
+using faiss_amd::METRIC_Linf;
+using faiss_amd::METRIC_Lp;
+using faiss_amd::METRIC_Canberra;
+using faiss_amd::METRIC_BrayCurtis;
+using faiss_amd::METRIC_JensenShannon;
+using faiss_amd::METRIC_Jaccard;
+using faiss_amd::METRIC_NaNEuclidean;
+using faiss_amd::METRIC_ABS_INNER_PRODUCT;
+using faiss_amd::is_similarity_metric;
 
 // faiss/impl/FaissException.h
 using faiss_amd::FaissException;

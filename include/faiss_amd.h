@@ -345,6 +345,9 @@ struct IndexFlat : Index {
     // direct per-row form over its members (exhaustive_*_seq)
     void search_selected(idx_t n, const float* x, int ldx, idx_t k, float* distances,
                          idx_t* labels, const IDSelector* sel, hipStream_t stream) const;
+    // a metric other than L2 / inner product (faiss/IndexFlat.cpp:55-67)
+    void search_extra_metric(idx_t n, const float* x, int ldx, idx_t k, float* distances,
+                             idx_t* labels, hipStream_t stream) const;
     mutable DeviceBuffer s_selids_, s_selmask_;  // 0 .. ntotal - 1 (int64) and membership
     mutable idx_t selids_n_ = 0;
 };

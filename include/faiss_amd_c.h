@@ -37,6 +37,16 @@ typedef faiss_idx_t idx_t;   /* reference c_api/faiss_c.h:18 */
 typedef enum FaissMetricType {
     METRIC_INNER_PRODUCT = 0,
     METRIC_L2 = 1,
+    /* IndexFlat only */
+    METRIC_L1,
+    METRIC_Linf,
+    METRIC_Lp,
+    METRIC_Canberra = 20,
+    METRIC_BrayCurtis,
+    METRIC_JensenShannon,
+    METRIC_Jaccard,
+    METRIC_NaNEuclidean,
+    METRIC_ABS_INNER_PRODUCT,
 } FaissMetricType;
 
 /* reference c_api/error_c.h:19-32 */
@@ -72,6 +82,9 @@ int faiss_Index_d(const FaissIndex*);                       /* Index_c.h:53 */
 int faiss_Index_is_trained(const FaissIndex*);              /* Index_c.h:56 */
 idx_t faiss_Index_ntotal(const FaissIndex*);                /* Index_c.h:59 */
 FaissMetricType faiss_Index_metric_type(const FaissIndex*); /* Index_c.h:62 */
+/* Index::metric_arg (the exponent of METRIC_Lp) */
+float faiss_amd_Index_metric_arg(const FaissIndex*);
+void faiss_amd_Index_set_metric_arg(FaissIndex*, float);
 int faiss_Index_verbose(const FaissIndex*);                 /* Index_c.h:64 */
 void faiss_Index_set_verbose(FaissIndex*, int);             /* Index_c.h:64 */
 
