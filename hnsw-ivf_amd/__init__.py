@@ -328,6 +328,10 @@ def _declare(L):
         "faiss_amd_IndexPQ_pq_centroids": (None, [_P, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t)]),
         "faiss_amd_IndexPQ_codes": (None, [_P, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
         "faiss_amd_IndexPQ_set_content": (C.c_int, [_P, C.c_void_p, C.c_int64, C.c_void_p]),
+        "faiss_amd_IndexSQ_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+        "faiss_amd_IndexSQ_trained": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_size_t)]),
+        "faiss_amd_IndexSQ_codes": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
+        "faiss_amd_IndexSQ_set_content": (C.c_int, [_P, C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p]),
         "faiss_amd_SearchParametersPQ_new": (C.c_int, [C.c_int, C.c_int, _P, C.POINTER(_P)]),
         "faiss_amd_SearchParametersPQ_free": (None, [_P]),
         "faiss_amd_indexPQ_stats": (None, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -997,8 +1001,67 @@ class IndexIVFScalarQuantizer(IndexIVF):
             self.h, x.shape[0], _ptr(x), _ptr(ids) if ids is not None else None, _ptr(pre)))
 
 
+class IndexScalarQuantizer(Index):
+    """faiss.IndexScalarQuantizer: a flat array of QT_8bit / QT_fp16 codes
+    (d % 8 == 0), searched exhaustively on the GPU in the reference's fp32
+    order.  index_factory(d, "SQ8" / "SQfp16") builds it."""
+
+    def __init__(self, d=None, qtype=QT_8bit, metric=METRIC_L2, handle=None, owner=None):
+        if handle is None:
+            desc = {QT_8bit: "SQ8", QT_fp16: "SQfp16", 1: "SQ4", 6: "SQ6", 7: "SQbf16",
+                    5: "SQ8_direct", 8: "SQ8_direct_signed"}[int(qtype)]
+            p = C.c_void_p()
+            _check(lib().faiss_index_factory(C.byref(p), d, desc.encode(), metric))
+            handle = p
+        super().__init__(handle, owner)
+
+    def _info(self):
+        qt, cs = C.c_int(), C.c_size_t()
+        _check(lib().faiss_amd_IndexSQ_info(self.h, C.byref(qt), C.byref(cs)))
+        return qt.value, cs.value
+
+    @property
+    def qtype(self):
+        return self._info()[0]
+
+    @property
+    def code_size(self):
+        return self._info()[1]
+
+    def sq_trained(self):
+        """A copy of sq.trained (QT_8bit: vmin [d] then vdiff [d]; QT_fp16: empty)."""
+        p, n = C.POINTER(C.c_float)(), C.c_size_t(0)
+        _check(lib().faiss_amd_IndexSQ_trained(self.h, C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=np.float32)
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy()
+
+    @property
+    def codes(self):
+        """A copy of the code array, [ntotal][code_size] uint8."""
+        p, n = C.POINTER(C.c_uint8)(), C.c_size_t(0)
+        _check(lib().faiss_amd_IndexSQ_codes(self.h, C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return np.zeros((0, self.code_size), np.uint8)
+        return np.ctypeslib.as_array(p, shape=(n.value,)).reshape(-1, self.code_size).copy()
+
+    def set_content(self, trained=None, codes=None):
+        """Assign sq.trained (the index becomes trained) and / or the whole
+        code array ([n][code_size] uint8; ntotal = n)."""
+        t = k = None
+        n = 0
+        if trained is not None:
+            t = np.ascontiguousarray(trained, dtype=np.float32).reshape(-1)
+        if codes is not None:
+            k = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, self.code_size)
+            n = k.shape[0]
+        _check(lib().faiss_amd_IndexSQ_set_content(
+            self.h, t.ctypes.data if t is not None else None, t.size if t is not None else 0, n,
+            k.ctypes.data if k is not None else None))
+
+
 # faiss/IndexPQ.h Search_type_t
-ST_PQ, ST_HE, ST_generalized_HE, ST_SDC, ST_polysemous, ST_polysemous_generalize = range(6)
+ST_PQ,ST_HE, ST_generalized_HE, ST_SDC, ST_polysemous, ST_polysemous_generalize = range(6)
 
 
 class IndexPQ(Index):
@@ -1720,6 +1783,7 @@ def _wrap(h, owner=None):
            "IndexIVFScalarQuantizer": IndexIVFScalarQuantizer,
            "IndexHNSWFlat": IndexHNSWFlat, "IndexFlat": IndexFlat,
            "IndexRefineFlat": IndexRefineFlat, "IndexPQ": IndexPQ,
+           "IndexScalarQuantizer": IndexScalarQuantizer,
            "IndexPreTransform": IndexPreTransform}.get(t)
     if cls is None:
         return Index(h, owner)

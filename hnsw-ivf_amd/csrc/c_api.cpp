@@ -476,6 +476,35 @@ int faiss_amd_IndexPQ_set_content(FaissIndexPQ* index, const float* centroids, i
     C_TRY PQm(index)->set_content(centroids, n, codes);
     C_CATCH
 }
+// ---------------- IndexScalarQuantizer (the flat class)
+static IndexScalarQuantizer* SQm(const FaissIndex* i) {
+    auto r = dynamic_cast<IndexScalarQuantizer*>(const_cast<Index*>(IX(i)));
+    FAISS_THROW_IF_NOT_MSG(r, "not an IndexScalarQuantizer");
+    return r;
+}
+int faiss_amd_IndexSQ_info(const FaissIndex* index, int* qtype, size_t* code_size) {
+    C_TRY auto sq = SQm(index);
+    *qtype = (int)sq->sq.qtype;
+    *code_size = sq->code_size;
+    C_CATCH
+}
+int faiss_amd_IndexSQ_trained(FaissIndex* index, float** p, size_t* n) {
+    C_TRY auto sq = SQm(index);
+    *p = sq->sq.trained.data();
+    *n = sq->sq.trained.size();
+    C_CATCH
+}
+int faiss_amd_IndexSQ_codes(FaissIndex* index, uint8_t** p, size_t* n) {
+    C_TRY auto sq = SQm(index);
+    *p = sq->codes.data();
+    *n = sq->codes.size();
+    C_CATCH
+}
+int faiss_amd_IndexSQ_set_content(FaissIndex* index, const float* trained, size_t nt, idx_t n,
+                                  const uint8_t* codes) {
+    C_TRY SQm(index)->set_content(trained, nt, n, codes);
+    C_CATCH
+}
 int faiss_amd_SearchParametersPQ_new(int search_type, int polysemous_ht, FaissIDSelector* sel,
                                      FaissSearchParameters** p_sp) {
     C_TRY auto sp = new PQParamsC();

@@ -176,6 +176,7 @@ const char* index_type_name(const Index* x) {
     if (dynamic_cast<const IndexHNSW*>(x)) return "IndexHNSWFlat";
     if (dynamic_cast<const IndexFlat*>(x)) return "IndexFlat";
     if (dynamic_cast<const IndexPQ*>(x)) return "IndexPQ";
+    if (dynamic_cast<const IndexScalarQuantizer*>(x)) return "IndexScalarQuantizer";
     return "Index";
 }
 

@@ -603,6 +603,17 @@ void write_index_impl(const Index* idx, Writer& w) {
         w.one<int32_t>((int32_t)ipq->search_type);
         w.one<bool>(ipq->encode_signs);
         w.one<int32_t>(ipq->polysemous_ht);
+    } else if (auto isq = dynamic_cast<const IndexScalarQuantizer*>(idx)) {
+        // faiss/impl/index_write.cpp:234-241, 596-603
+        w.one(fourcc("IxSQ"));
+        write_header(isq, w);
+        w.one<int32_t>((int32_t)isq->sq.qtype);
+        w.one<int32_t>((int32_t)isq->sq.rangestat);
+        w.one<float>(isq->sq.rangestat_arg);
+        w.one<size_t>(isq->sq.d);
+        w.one<size_t>(isq->sq.code_size);
+        w.vec(isq->sq.trained);
+        w.vec(isq->codes);
     } else if (auto rf = dynamic_cast<const IndexRefine*>(idx)) {
         // faiss/impl/index_write.cpp:744-752
         w.one(fourcc("IxRF"));
@@ -754,6 +765,32 @@ Index* read_index_impl(Reader& r, int io_flags) {
         }
         // the two old tags stored INNER_PRODUCT while searching L2
         if (h != fourcc("IxPq")) ix->metric_type = METRIC_L2;
+        return ix.release();
+    }
+    if (h == fourcc("IxSQ")) {
+        // faiss/impl/index_read.cpp:353-361, 788-794
+        Header hd = read_header(r);
+        const int32_t qtype = r.one<int32_t>();
+        const int32_t rangestat = r.one<int32_t>();
+        const float rs_arg = r.one<float>();
+        const size_t sd = r.one<size_t>(), scs = r.one<size_t>();
+        // the constructor throws, naming the qtype / d, unless served
+        ScalarQuantizer::check_supported(qtype, (size_t)hd.d);
+        FAISS_THROW_IF_NOT_FMT(sd == (size_t)hd.d, "IxSQ: ScalarQuantizer d = %zu, index d = %d", sd,
+                               hd.d);
+        auto ix = std::make_unique<IndexScalarQuantizer>(
+                hd.d, (ScalarQuantizer::QuantizerType)qtype, (MetricType)hd.metric);
+        apply_header(ix.get(), hd);
+        ix->sq.rangestat = (ScalarQuantizer::RangeStat)rangestat;
+        ix->sq.rangestat_arg = rs_arg;
+        r.vec(ix->sq.trained);
+        FAISS_THROW_IF_NOT_FMT(scs == ix->sq.code_size, "IxSQ: code_size %zu, expected %zu", scs,
+                               ix->sq.code_size);
+        const size_t nt = qtype == ScalarQuantizer::QT_8bit ? 2 * (size_t)hd.d : 0;
+        FAISS_THROW_IF_NOT_FMT(!hd.is_trained || ix->sq.trained.size() == nt,
+                               "IxSQ: %zu trained values, expected %zu", ix->sq.trained.size(), nt);
+        r.vec(ix->codes);
+        FAISS_THROW_IF_NOT(ix->codes.size() == (size_t)hd.ntotal * ix->code_size);
         return ix.release();
     }
     if (h == fourcc("IxRF")) {
@@ -1093,6 +1130,25 @@ Index* factory_no_transform(int d, const char* description, MetricType metric) {
 }  // namespace
 
 namespace {
+// faiss/index_factory.cpp sq_types: the qtype of an "SQ..." token, -1 for none.
+// The constructors reject the qtypes and dimensions this path does not serve,
+// naming them.
+int sq_qtype_of(const std::string& name) {
+    static const struct {
+        const char* name;
+        ScalarQuantizer::QuantizerType qt;
+    } sq_types[] = {{"SQ8", ScalarQuantizer::QT_8bit},
+                    {"SQ4", ScalarQuantizer::QT_4bit},
+                    {"SQ6", ScalarQuantizer::QT_6bit},
+                    {"SQfp16", ScalarQuantizer::QT_fp16},
+                    {"SQbf16", ScalarQuantizer::QT_bf16},
+                    {"SQ8_direct_signed", ScalarQuantizer::QT_8bit_direct_signed},
+                    {"SQ8_direct", ScalarQuantizer::QT_8bit_direct}};
+    for (const auto& t : sq_types)
+        if (name == t.name) return (int)t.qt;
+    return -1;
+}
+
 Index* factory_plain(int d, const std::string& s_in, MetricType metric) {
     std::string s(s_in);
     auto parse_int = [&](size_t& pos) {
@@ -1123,6 +1179,8 @@ Index* factory_plain(int d, const std::string& s_in, MetricType metric) {
         FAISS_THROW_IF_NOT_MSG(pos == s.size(), "unsupported PQ spec " + s);
         return new IndexPQ(d, M, nbits, metric);
     }
+    if (const int qt = sq_qtype_of(s); qt >= 0)  // faiss/index_factory.cpp:560-568
+        return new IndexScalarQuantizer(d, (ScalarQuantizer::QuantizerType)qt, metric);
     FAISS_THROW_IF_NOT_MSG(s.rfind("IVF", 0) == 0, "unsupported index_factory string " + s);
     size_t pos = 3;
     size_t nlist = (size_t)parse_int(pos);
@@ -1162,23 +1220,10 @@ Index* factory_plain(int d, const std::string& s_in, MetricType metric) {
             FAISS_THROW_IF_NOT_MSG(tail.empty() || tail == "np", "unsupported PQ spec " + enc);
             ivf = new IndexIVFPQ(q, d, nlist, M, nbits, metric);
         } else if (enc.rfind("SQ", 0) == 0) {
-            // faiss/index_factory.cpp sq_types; the constructor rejects the
-            // qtypes and dimensions this path does not serve, naming them
-            static const struct {
-                const char* name;
-                ScalarQuantizer::QuantizerType qt;
-            } sq_types[] = {{"SQ8", ScalarQuantizer::QT_8bit},
-                            {"SQ4", ScalarQuantizer::QT_4bit},
-                            {"SQ6", ScalarQuantizer::QT_6bit},
-                            {"SQfp16", ScalarQuantizer::QT_fp16},
-                            {"SQbf16", ScalarQuantizer::QT_bf16},
-                            {"SQ8_direct_signed", ScalarQuantizer::QT_8bit_direct_signed},
-                            {"SQ8_direct", ScalarQuantizer::QT_8bit_direct}};
-            int found = -1;
-            for (int i = 0; i < 7; i++)
-                if (enc == sq_types[i].name) found = i;
-            FAISS_THROW_IF_NOT_MSG(found >= 0, "unsupported IVF encoding " + enc);
-            ivf = new IndexIVFScalarQuantizer(q, d, nlist, sq_types[found].qt, metric);
+            const int qt = sq_qtype_of(enc);
+            FAISS_THROW_IF_NOT_MSG(qt >= 0, "unsupported IVF encoding " + enc);
+            ivf = new IndexIVFScalarQuantizer(q, d, nlist, (ScalarQuantizer::QuantizerType)qt,
+                                              metric);
         } else {
             FAISS_THROW_MSG("unsupported IVF encoding " + enc);
         }

@@ -352,6 +352,28 @@ void pq_flat_search(const PQFlatArgs& a, DeviceBuffer& s_part, DeviceBuffer& s_t
 // queries a work group holds tables for at this shape (*global_tables: they
 // do not fit the LDS and live in global scratch)
 int pq_flat_queries_per_group(const PQFlatArgs& a, bool* global_tables = nullptr);
+// IndexScalarQuantizer: exact k-NN over a flat array of SQ8 / SQfp16 codes
+// (kernels_sq_flat.hip): a 64 x 64 VALU tile in the evaluation order of
+// sq_ref.h that decodes each code once per query tile, dense distance rows of
+// sq_flat_query_chunk queries at a time, then select_rows_exact.  Rows are
+// their own labels; D / I [n][k] as the reference heap leaves them, pads
+// (FLT_MAX / -FLT_MAX, -1).  d % 8 == 0, 1 <= k <= kMaxKExact.  The scratch
+// buffers grow on demand and are never shrunk.
+struct SQFlatArgs {
+    const float* x = nullptr;  // [n][ldx] queries
+    int ldx = 0, d = 0;
+    int64_t n = 0;
+    int qtype = 0;                   // SQ_QT_8bit / SQ_QT_fp16 (sq_ref.h)
+    const float* trained = nullptr;  // vmin [d] | vdiff [d] (QT_8bit)
+    const uint8_t* codes = nullptr;  // [ntotal] rows of d (8bit) / 2 d (fp16) bytes
+    int64_t ntotal = 0;
+    int k = 0, l2 = 1;
+    const uint8_t* mask = nullptr;  // [ntotal] selector membership; null: every row
+};
+void sq_flat_search(const SQFlatArgs& a, DeviceBuffer& s_dense, DeviceBuffer& s_sel, float* D,
+                    int64_t* I, hipStream_t s, KernelTimes* kt = nullptr);
+// queries per pass over the codes: 256 MiB of dense rows, whole 64-query tiles
+int64_t sq_flat_query_chunk(int64_t n, int64_t ntotal);
 // ---------------- binary indexes (kernels_binary.hip) ----------------
 // Hamming k-NN over bit vectors of d bits stored as W = ceil(d / 32) zero-padded
 // dwords per row.  D / I [n][k]: int32 distances, pads (INT32_MAX, -1).

@@ -94,8 +94,9 @@ using faiss_amd::IndexIVFFlat;
 using faiss_amd::IndexIVFPQ;
 using faiss_amd::ProductQuantizer;
 
-// faiss/IndexScalarQuantizer.h (the IVF class only), faiss/impl/ScalarQuantizer.h
+// faiss/IndexScalarQuantizer.h, faiss/impl/ScalarQuantizer.h
 using faiss_amd::IndexIVFScalarQuantizer;
+using faiss_amd::IndexScalarQuantizer;
 using faiss_amd::ScalarQuantizer;
 
 // faiss/IndexPQ.h

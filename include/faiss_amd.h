@@ -1017,6 +1017,48 @@ struct IndexIVFScalarQuantizer : IndexIVF {
     mutable DeviceBuffer d_trained_, d_cent_;
 };
 
+// faiss/IndexScalarQuantizer.h:24-63 over IndexFlatCodes: the flat array of
+// scalar-quantizer codes, searched exhaustively by kern::sq_flat_search
+// (kernels_sq_flat.hip: each code decoded once per tile of 64 queries, the
+// reference scanner's fp32 evaluation order).  QT_8bit and QT_fp16 with
+// d % 8 == 0, L2 and inner product; params->sel is asked about row numbers.
+struct IndexScalarQuantizer : Index {
+    ScalarQuantizer sq;
+    std::vector<uint8_t> codes;  // [ntotal][code_size] (IndexFlatCodes::codes)
+    size_t code_size = 0;
+
+    // throws, naming the qtype / d, unless served (ScalarQuantizer::check_supported)
+    IndexScalarQuantizer(int d, ScalarQuantizer::QuantizerType qtype,
+                         MetricType metric = METRIC_L2);
+    IndexScalarQuantizer();
+    void train(idx_t n, const float* x) override;  // sq.train on the vectors themselves
+    void add(idx_t n, const float* x) override;
+    void search_device(idx_t n, const float* x, int ldx, idx_t k, float* distances,
+                       idx_t* labels, const SearchParameters* params,
+                       hipStream_t stream) const override;
+    void reset() override;
+    // ScalarQuantizer::decode: the true-division form, not the scanner's
+    void reconstruct(idx_t key, float* recons) const override;
+    void reconstruct_n(idx_t i0, idx_t ni, float* recons) const override;
+    // faiss/IndexFlatCodes.cpp:53-73: sel is asked about row numbers
+    size_t remove_ids(const IDSelector& sel) override;
+    // throws "IndexScalarQuantizer: range search not implemented"
+    void range_search(idx_t n, const float* x, float radius, RangeSearchResult* result,
+                      const SearchParameters* params = nullptr) const override;
+    void sync_device() const override;
+    // what assigning the public fields does, plus the bookkeeping: sq.trained
+    // (nt values, null: kept; is_trained becomes true), then the whole code
+    // array, n rows (null: kept); the next search uploads them
+    void set_content(const float* trained, size_t nt, idx_t n, const uint8_t* codes);
+
+   protected:
+    mutable std::recursive_mutex mu_;
+    mutable StreamOrder order_;
+    mutable bool dirty_ = true;
+    mutable DeviceBuffer d_codes_, d_trained_, s_dense_, s_sel_, s_rowids_, s_mask_;
+    mutable idx_t rowids_n_ = 0;
+};
+
 // ---------------------------------------------------------------- IndexPQ
 // faiss/IndexPQ.h:19-150 over IndexFlatCodes: the flat array of PQ codes,
 // searched exhaustively by kern::pq_flat_search (kernels_pq_flat.hip: the
@@ -1389,7 +1431,8 @@ Index* read_index(const char* fname, int io_flags = 0);
 void write_index_ondisk(const Index* idx, const char* fname, const char* lists_fname);
 Index* read_index(FILE* f, int io_flags = 0);
 
-// faiss/index_factory.h (subset: Flat, PQm[xb], IVFn[_HNSWm],Flat|PQm[xb][np]|SQ8|SQfp16,
+// faiss/index_factory.h (subset: Flat, PQm[xb], SQ8, SQfp16,
+// IVFn[_HNSWm],Flat|PQm[xb][np]|SQ8|SQfp16,
 // HNSWm, each optionally followed by ",RFlat" / ",Refine(Flat)")
 Index* index_factory(int d, const char* description, MetricType metric = METRIC_L2);
 

@@ -273,6 +273,25 @@ void faiss_amd_SearchParametersPQ_free(FaissSearchParameters* obj);
 void faiss_amd_indexPQ_stats(size_t* nq, size_t* ncode);
 void faiss_amd_indexPQ_stats_reset(void);
 
+/* ---------------- the flat scalar-quantizer index (faiss/IndexScalarQuantizer.h:
+ * 24-63) ----------------
+ * Made by faiss_index_factory(d, "SQ8" / "SQfp16") or read from a file tagged
+ * IxSQ; faiss_amd_Index_type names its class.  train, add, search (with an
+ * IDSelector through faiss_Index_search_with_params), reset, reconstruct and
+ * remove_ids are the faiss_Index_* functions.  QT_8bit and QT_fp16 with
+ * d % 8 == 0, L2 and inner product. */
+/* sq.qtype and code_size */
+int faiss_amd_IndexSQ_info(const FaissIndex* index, int* qtype, size_t* code_size);
+/* pointers to the host fields sq.trained (QT_8bit: vmin [d] | vdiff [d];
+ * QT_fp16: empty) and codes [ntotal][code_size] */
+int faiss_amd_IndexSQ_trained(FaissIndex* index, float** p_trained, size_t* p_size);
+int faiss_amd_IndexSQ_codes(FaissIndex* index, uint8_t** p_codes, size_t* p_size);
+/* what assigning the reference's public fields does: the trained values (nt of
+ * them; null: kept; is_trained becomes true) and the whole code array (n rows;
+ * null: kept) */
+int faiss_amd_IndexSQ_set_content(FaissIndex* index, const float* trained, size_t nt, idx_t n,
+                                  const uint8_t* codes);
+
 /* ---------------- IndexRefineFlat (c_api/IndexFlat_c.h:89-107) ----------------
  * Searches k * k_factor candidates in base_index (a fast, compressed index)
  * and re-ranks them with exact distances from a flat copy of the vectors. */
@@ -643,9 +662,11 @@ int faiss_amd_IndexIVFPQ_set_by_residual(FaissIndexIVFPQ* index, int v);
 /* ---------------- IndexIVFScalarQuantizer (c_api/IndexScalarQuantizer_c.h) -
  * The IVF declarations of that header (:51 to its end).  QT_8bit and QT_fp16
  * with d % 8 == 0 are served; a constructor given anything else returns -2
- * with the qtype / d in faiss_get_last_error().  The non-IVF
- * IndexScalarQuantizer functions (:36-49) are not declared: a caller of those
- * fails to compile rather than at run time. */
+ * with the qtype / d in faiss_get_last_error().  The non-IVF class,
+ * IndexScalarQuantizer, is served too, but its C functions (:36-49) are not
+ * declared (a caller of those fails to compile rather than at run time): it
+ * is made by faiss_index_factory ("SQ8", "SQfp16") or read from an IxSQ file
+ * and used through the faiss_Index_* functions; see faiss_amd_IndexSQ_*. */
 /* IndexScalarQuantizer_c.h:20-31 */
 typedef enum FaissQuantizerType {
     QT_8bit,
